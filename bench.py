@@ -27,8 +27,12 @@ mismatch); each rank also compares its decoded piece with its source.
 Prints ONE JSON line on rank 0: value = uncompressed GiB of the whole job /
 (compress + decompress time), the per-direction rates, the encode kernel's
 roofline (HIP events on the library's launch stream; HBM traffic from the
-committed PMC profile of this same configuration, calibrated) and the CPU
-baseline (lz4mt-shaped pipeline on the host cores over liblz4 when present).
+committed PMC profile of this same configuration, calibrated).  A plain run
+does only that: set-up, warm-up, the timed steps, the line.
+
+--full adds the CPU baseline (lz4mt-shaped pipeline on the host cores over
+liblz4 when present; seconds of host time), ``cpu_baseline`` in the line.
+--dump-outputs DIR writes what the last timed step computed (dump_outputs).
 """
 import argparse
 import contextlib
@@ -73,7 +77,13 @@ def parse():
                    help="default lz4mt flags (FLG.2 content checksum, no block checksum) instead of -Sx -BX")
     p.add_argument("--level", type=int, default=0, help="compression level: 3..9 = LZ4-HC (not the headline)")
     p.add_argument("--block-dependent", action="store_true", help="-BD frames (serial; not the headline)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: the CPU baseline of this run's codec "
+                        "(a plain run reports cpu_baseline: null)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step computed (the frame and the decoded "
+                        "bytes: sizes, chunk digests, fixed seeded samples) as DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     p.add_argument("--cpu-mib", type=int, default=1024, help="CPU baseline sample (MiB, all threads)")
     p.add_argument("--gather", choices=["streamed", "after"], default="streamed",
                    help="N > 1: stream the shards' records to rank 0 while they encode (dist.compress_gather_streamed), "
@@ -253,6 +263,33 @@ def stdout_to_stderr():
         sys.stdout.flush()
         os.dup2(saved, 1)
         os.close(saved)
+
+
+DUMP_SAMPLE = 1 << 21    # sampled bytes per array (8 MiB as float32)
+DUMP_HEAD = 1 << 20      # leading bytes kept whole
+DUMP_CHUNK = 16 << 20    # bytes per XXH32 digest
+
+
+def dump_outputs(dirname, frame, decoded):
+    """--dump-outputs: what the last timed step handed its caller, as
+    DIR/<name>.npy (float64 for sizes and digests, float32 for bytes; under
+    40 MB in all).  For the frame (None when only the decompression is timed)
+    and for the decoded bytes: the length, the XXH32 of every 16 MiB chunk
+    (every byte counts), the first 1 MiB, and the bytes at 2 Mi positions
+    drawn once from a fixed seed over the array's length."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t, seed in (("frame", frame, 1), ("decoded", decoded, 2)):
+        if t is None:
+            continue
+        n = t.numel()
+        dig = (L.xxh32_chunks(t, DUMP_CHUNK).to(torch.int64) & 0xFFFFFFFF) if n else torch.zeros(0, dtype=torch.int64)
+        idx = np.sort(np.random.default_rng(seed).integers(0, max(n, 1), size=DUMP_SAMPLE, dtype=np.int64))
+        sample = t[torch.from_numpy(idx).to(t.device)] if n else t[:0]
+        np.save(os.path.join(dirname, f"{name}_bytes.npy"), np.array([n], dtype=np.float64))
+        np.save(os.path.join(dirname, f"{name}_xxh32_16MiB.npy"), dig.cpu().numpy().astype(np.float64))
+        np.save(os.path.join(dirname, f"{name}_head.npy"), t[:DUMP_HEAD].cpu().numpy().astype(np.float32))
+        np.save(os.path.join(dirname, f"{name}_sample.npy"), sample.cpu().numpy().astype(np.float32))
 
 
 def frame_encoder(bm):
@@ -742,6 +779,9 @@ def run(a, guard, world, rank, local, distributed):
     tc, td, ts, tg = R["tc"], R["td"], R["ts"], R["tg"]
     enc_ms, dec_ms, frame_len, exposed_ms = R["enc_ms"], R["dec_ms"], R["frame_len"], R["exposed_ms"]
     rounds, tails, scat, full, own_body = R["rounds"], R["tails"], R["scat"], R["full"], R["own_body"]
+    if a.dump_outputs and rank == 0:   # the last step's frame (N > 1: the stitched one) and rank 0's decoded bytes
+        dump_outputs(a.dump_outputs, None if a.decompress_only else full if distributed else frame_buf[:frame_len],
+                     out[:n])
     if distributed:
         mem["after_verify_max_allocated_GiB"] = round(torch.cuda.max_memory_allocated(dev) / GiB, 2)
         t = torch.tensor([tc, td, ts, tg, 0.0 if ok else 1.0], dtype=torch.float64, device=dev)
@@ -787,7 +827,7 @@ def run(a, guard, world, rank, local, distributed):
         roof = dec_roof
     if rank == 0:
         cpu = None
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             cpu = cpu_baseline(a.cpu_mib if a.level < 3 and not a.block_dependent else min(a.cpu_mib, 256),
                                a.block_id, sck, a.level, a.block_dependent)
         flags = ("default flags (FLG.2 content checksum)" if sck else "-Sx -BX") + \

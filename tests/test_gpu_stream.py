@@ -673,27 +673,51 @@ def test_streamed_writer_stall_parks_the_grid(monkeypatch, capfd):
         time.sleep(0.1)
         timed_work()
 
+    begun = []   # the write hooks of the running call that have started
+
+    def write_hook():
+        begun.append(1)
+        timed_work()
+
+    def paced_read(hooks):
+        """10 ms per read(); 30 ms (still below the park threshold) while a
+        write hook of this call has yet to start."""
+        def f():
+            time.sleep(0.01 if len(begun) >= hooks else 0.03)
+        return f
+
     _lds_heavy_gpu_work()
-    data = oracle.gen_synthetic(24 << 20, 43)
+    # A grid whose last block is read and encoded has left the device, and a
+    # hook that starts then waits for nothing.  A record reaches the writer
+    # 0.05 - 0.7 s after its read(), so the reader must not finish before the
+    # hooks have begun: 64 blocks, the hooks in the first 21 records, and the
+    # reads go on slowly (paced_read) until every write hook has started
+    nblk = 64
+    data = oracle.gen_synthetic(nblk << 20, 43)
     frame = oracle.compress_frame(data, oracle.params(6, True, True))
     for rings in ((256, 512), (8, 8)):
         monkeypatch.setenv("LZ4MT_AMD_STREAM_IN", str(rings[0]))
         monkeypatch.setenv("LZ4MT_AMD_STREAM_OUT", str(rings[1]))
+        # (the rings of this size are allocated by the first call: not under a hook's clock)
+        r, _ = _hook_io(L.lib.lz4mtCompress, data[:1 << 20], L.make_sd(6, True, True), {})
+        assert r == 0, L.result_to_string(r)
         # compress: three write() calls per record (size word, payload, checksum) after the header's
         # the reader is kept busy (10 ms per read(), below the park threshold),
         # so the grid's idle waves sit in their input waits -- holding the LDS
         # -- while the writer stalls, as in a real pipe
-        for rh, wh in (({}, {2: timed_work}), ({}, {5: timed_work, 40: timed_work}),
-                       ({6: slow_then_work}, {8: timed_work}), ({}, {62: timed_work})):
-            rh = {**{k: (lambda: time.sleep(0.01)) for k in range(1, 26)}, **rh}
+        for rh, wh in (({}, {2: write_hook}), ({}, {5: write_hook, 40: write_hook}),
+                       ({6: slow_then_work}, {8: write_hook}), ({}, {62: write_hook})):
+            del begun[:]
+            rh = {**{k: paced_read(len(wh)) for k in range(1, nblk + 2)}, **rh}
             t0 = time.time()
             r, got = _hook_io(L.lib.lz4mtCompress, data, L.make_sd(6, True, True), rh, wh)
             assert r == 0 and got == frame, (rings, sorted(wh), L.result_to_string(r))
             assert time.time() - t0 < 60
         # decompress: one write() per decoded block
-        for rh, wh in (({}, {1: timed_work}), ({}, {3: timed_work, 14: timed_work}),
-                       ({10: slow_then_work}, {4: timed_work}), ({}, {18: timed_work})):
-            rh = {**{k: (lambda: time.sleep(0.01)) for k in range(2, 75, 3)}, **rh}   # the data reads
+        for rh, wh in (({}, {1: write_hook}), ({}, {3: write_hook, 14: write_hook}),
+                       ({10: slow_then_work}, {4: write_hook}), ({}, {18: write_hook})):
+            del begun[:]
+            rh = {**{k: paced_read(len(wh)) for k in range(2, 3 * nblk + 3, 3)}, **rh}   # the data reads
             r, got = _hook_io(L.lib.lz4mtDecompress, frame, L.init_stream_descriptor(), rh, wh)
             assert r == 0 and got == data, (rings, sorted(wh), L.result_to_string(r))
     err = capfd.readouterr().err

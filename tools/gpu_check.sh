@@ -16,7 +16,7 @@ else
       --timeout-method thread > "$out/pytest.log" 2>&1
 fi
 tail -3 "$out/pytest.log"
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > "$out/bench.json" 2> "$out/bench.err"
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 > "$out/bench.json" 2> "$out/bench.err"
 cat "$out/bench.json"
 timeout -k 10 300 python3 bench.py --steps 3 --warmup 1 --stream-checksum --no-cpu-baseline > "$out/bench_sck.json" 2> "$out/bench_sck.err"
 cat "$out/bench_sck.json"

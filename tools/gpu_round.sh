@@ -4,7 +4,7 @@
 # usage (from the repo root on the box): bash tools/gpu_round.sh <tag> <step>...
 #   tests   pytest -m gpu (every GPU test file)
 #   tdist   pytest -m gpu tests/test_gpu_dist.py (the multi-rank paths) only
-#   bench   the default 1-GPU bench line (driver shape: --steps 20 --warmup 5)
+#   bench   the default 1-GPU bench line with the CPU baseline (--full --steps 20 --warmup 5)
 #   trace   rocprofv3 kernel-trace stats of a 5-step bench run
 #   sq      SQ counters of the encoder / decoder (tools/kprof.py 2) + the window count (tools/kstats.py 2)
 #   pmc     FETCH_SIZE / WRITE_SIZE passes (tools/prof.sh without its trace)
@@ -43,7 +43,7 @@ for step in "$@"; do
           > "$out/pytest_dist.log" 2>&1 || { tail -40 "$out/pytest_dist.log"; exit 1; }
       tail -2 "$out/pytest_dist.log" ;;
     bench)
-      timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > "$out/bench.json" 2> "$out/bench.err"
+      timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 > "$out/bench.json" 2> "$out/bench.err"
       cat "$out/bench.json" ;;
     trace)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -T -f csv -d "$out/trace" -o trace -- \
