@@ -634,13 +634,22 @@ bool host_wait(P pred, Q stop) {
 // block in its own HBM buffers with a descriptor in dPend; waves working on
 // a block finish it and then do one of the two.  While parked the reader
 // publishes nothing (publish() below, under the mutex the park is set
-// under), so every block below the reader's next one was taken.  Other work
-// on the device -- a callback's own GPU calls included -- can then run.
+// under), so every block number a wave CLAIMED below the reader's next one
+// was taken.  Published blocks may still be unclaimed at a park: the reader
+// runs up to Rin blocks ahead of the last pull, and a wave that parks from
+// its output wait keeps its own block and claims no other -- with every wave
+// holding a block (a write() stall, or a read() stall behind a slow
+// writer), up to Rin published blocks have no owner.  Other work on the
+// device -- a callback's own GPU calls included -- can then run.
 // Within 10 ms of no callback being stalled any more, the monitor waits for
-// the parked grid to drain and launches it again at the reader's next block;
-// each wave first finishes the block it parked with.  The callbacks
-// themselves only stamp their start and end (atomics): the reader's one
-// publish per block is the only lock on the data path.
+// the parked grid to drain, reads the grid's block counter back and launches
+// the grid again at min(that counter, the reader's next block): numbers
+// claimed at or above the reader's next block were given up in an input
+// wait and hold nothing, every claimed number below it was taken, so the
+// minimum is the lowest block nobody took (tools/stream_model.py is the
+// protocol's model).  Each wave first finishes the block it parked with.
+// The callbacks themselves only stamp their start and end (atomics): the
+// reader's one publish per block is the only lock on the data path.
 uint64_t stream_wait_ticks() {
     return (uint64_t)env_int("LZ4MT_AMD_STREAM_TIMEOUT_S", 60, 1, 86400) * 100000000ull;   // 100 MHz
 }
@@ -707,24 +716,33 @@ class StreamMonitor {
         return (r >= 0 && t - r >= lim) ? "read()" : (w >= 0 && t - w >= lim) ? "write()" : nullptr;
     }
     // (mu_ held: nothing is published meanwhile) waits for the parked grid
-    // to drain -- every wave leaves by itself -- and launches it again at the
-    // reader's next block
+    // to drain -- every wave leaves by itself -- reads the grid's own block
+    // counter back and launches the grid again at the lowest block no wave
+    // took: min(device counter, the reader's next block)
     bool relaunch_locked() {
         if (hipStreamSynchronize(B_.st) != hipSuccess || __atomic_load_n(g_ + 4, __ATOMIC_ACQUIRE) != 0 ||
             __atomic_load_n(g_ + 1, __ATOMIC_ACQUIRE) != 0) {
             (void)hipGetLastError();
             return false;
         }
+        uint32_t devNext = 0;   // (the grid has drained: a 4-byte copy and a wait)
+        if (hipMemcpyAsync(&devNext, B_.dNext, 4, hipMemcpyDeviceToHost, B_.st) != hipSuccess ||
+            hipStreamSynchronize(B_.st) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        const uint32_t at = std::min(devNext, nextPub_);
         __atomic_store_n(g_ + 7, 0u, __ATOMIC_RELEASE);
         parked_ = false;
-        if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(B_.dNext), (int)nextPub_, 1, B_.st) != hipSuccess ||
+        if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(B_.dNext), (int)at, 1, B_.st) != hipSuccess ||
             launch_() != hipSuccess) {
             (void)hipGetLastError();
             return false;
         }
         if (const char* t = getenv("LZ4MT_AMD_PIPE_TRACE"); t && atoi(t) != 0)   // (read per event: rare)
-            fprintf(stderr, "lz4mt_amd: streamed grid parked while a %s stalled; relaunched at block %u\n",
-                    why_, nextPub_);
+            fprintf(stderr,
+                    "lz4mt_amd: streamed grid parked while a %s stalled; relaunched at block %u (reader at %u)\n",
+                    why_, at, nextPub_);
         return true;
     }
     void run() {
@@ -873,7 +891,7 @@ bool compress_streamed(Session& s, const Lz4MtStreamDescriptor* sd, HostXxh32& x
         }
         if (n <= 0) break;
         // never while the grid is parked (a read() or write() stalled): the
-        // reader relaunches it at b first, or waits for the writer to
+        // publish waits for the monitor's relaunch first
         if (!ka.publish(b, [&] {
                 st_rel(ic + 1, (uint32_t)n);
                 st_rel(ic, b + 1);

@@ -12,6 +12,7 @@ short reads are short blocks; a failing write() ends the call with an error
 and the grid drains (the next call works)."""
 import ctypes
 import random
+import re
 import struct
 
 import pytest
@@ -559,13 +560,16 @@ def test_streamed_decompress_damaged_vs_oracle(bid, sck, bck):
         assert out == ow, (it, kind, L.result_to_string(r), len(out), len(ow))
 
 
-def _hook_io(fn, data, sd, hooks, whooks=None):
+def _hook_io(fn, data, sd, hooks, whooks=None, st=None):
     """lz4mtCompress / lz4mtDecompress (MODE_DEVICE) with Python callbacks;
     hooks[k] runs inside the k-th read() call (1-based) before it returns,
-    whooks[k] inside the k-th write() call."""
+    whooks[k] inside the k-th write() call.  st: a dict of the caller's that
+    takes the call's counters (st["r"] / st["w"]: read() / write() calls so
+    far), for hooks that watch them."""
     from lz4mt_amd import _abi
     src = ctypes.create_string_buffer(bytes(data), max(len(data), 1))
-    st = {"pos": 0, "r": 0, "w": 0}
+    st = {} if st is None else st
+    st.update({"pos": 0, "r": 0, "w": 0})
     out = []
     whooks = whooks or {}
 
@@ -797,3 +801,161 @@ def test_streamed_compress_piped_into_streamed_decompress(monkeypatch):
     assert not alive, "compress | decompress through a pipe did not finish"
     assert res == {"c": 0, "d": 0}, res
     assert b"".join(out) == data
+
+
+# ---------------------------------------------------------------------------
+# Park / relaunch over a deep backlog: EVERY wave holds a finished block in
+# its output wait and the reader is Rin blocks ahead (a long stream into a
+# slow sink).  At the park the published blocks between the grid's own block
+# counter and the reader's next block have no owner; the relaunch has to start
+# at the grid's counter (tools/stream_model.py, tests/test_stream_model.py: a
+# relaunch at the reader's block loses them and the call ends in the wait
+# timeout).  One wave per CU, rings of 8 slots, N = 8 + W + 8 + 128 blocks of
+# 64 KiB (the byU16 stream kernel) and of 256 KiB (the v5 one).
+# Measured on an MI355X (W = 256, N = 400): the 12 cases take 14 s together,
+# fixtures included; every relaunch at block 264 against the reader's 272 (392
+# against 400 at the second stall, 268 / 269 against 273 behind the slow writer).
+# ---------------------------------------------------------------------------
+_RIN = _ROUT = 8
+_TRACE = re.compile(r"parked while a (read\(\)|write\(\)) stalled; relaunched at block (\d+) \(reader at (\d+)\)")
+_deep = {}
+
+
+def _deep_case(bid):
+    """(W, N, data, frame) for the block id, made once."""
+    if bid not in _deep:
+        W = torch.cuda.get_device_properties(0).multi_processor_count
+        N = _ROUT + W + _RIN + 128
+        data = oracle.gen_synthetic(N << (8 + 2 * bid), 50 + bid)
+        _deep[bid] = (W, N, data, oracle.compress_frame(data, oracle.params(bid, True, True)))
+    return _deep[bid]
+
+
+def _deep_env(monkeypatch):
+    monkeypatch.setenv("LZ4MT_AMD_STREAM_WAVES_PER_CU", "1")
+    monkeypatch.setenv("LZ4MT_AMD_STREAM_IN", str(_RIN))
+    monkeypatch.setenv("LZ4MT_AMD_STREAM_OUT", str(_ROUT))
+    # (the backlog has to be built before the park: at 50 ms the park can win the race)
+    monkeypatch.setenv("LZ4MT_AMD_STREAM_PARK_MS", "300")
+    monkeypatch.setenv("LZ4MT_AMD_PIPE_TRACE", "1")
+    # a lost block ends the call as LZ4MT_RESULT_ERROR in seconds, not in a minute
+    monkeypatch.setenv("LZ4MT_AMD_STREAM_TIMEOUT_S", "10")
+
+
+def _deep_run(engine, bid, hooks, whooks, st):
+    W, N, data, frame = _deep_case(bid)
+    if engine == "compress":
+        r, got = _hook_io(L.lib.lz4mtCompress, data, L.make_sd(bid, True, True), hooks, whooks, st)
+        want = frame
+    else:
+        r, got = _hook_io(L.lib.lz4mtDecompress, frame, L.init_stream_descriptor(), hooks, whooks, st)
+        want = data
+    assert r == 0, (engine, bid, L.result_to_string(r))
+    assert got == want, (engine, bid, len(got), len(want))
+
+
+def _record_write_call(engine, k):
+    """The first write() call (1-based) of record k: the compress writes the
+    header, then size word, payload and checksum per record; the decompress
+    one decoded block per call."""
+    return 2 + 3 * k if engine == "compress" else 1 + k
+
+
+def _until_reader_rests(st):
+    """A write() hook: returns once st["r"] has not moved for 0.5 s (the reader
+    is blocked on a full staging ring and the park, 300 ms, has fired); 5 s at
+    the most."""
+    import time
+
+    def hook():
+        t0 = t_last = time.time()
+        last = st["r"]
+        while time.time() - t0 < 5.0:
+            time.sleep(0.01)
+            if st["r"] != last:
+                last, t_last = st["r"], time.time()
+            elif time.time() - t_last >= 0.5:
+                return
+    return hook
+
+
+def _check_trace(capfd, why, at_least):
+    """The relaunches of the call from its trace lines: at_least of them
+    below the reader's block, charged to `why`."""
+    err = capfd.readouterr().err
+    tr = [(m[1], int(m[2]), int(m[3])) for m in _TRACE.finditer(err)]
+    with capfd.disabled():
+        print(f"relaunches (stalled callback, at block, reader at): {tr}")
+    assert f"a {why} stalled" in err, err[-2000:]
+    below = [t for t in tr if t[0] == why and t[1] < t[2]]
+    assert len(below) >= at_least, f"the deep-backlog regime was not reached: relaunches {tr}"
+
+
+_DEEP = [(e, b) for e in ("compress", "decompress") for b in (4, 5)]
+
+
+@pytest.mark.parametrize("engine,bid", _DEEP)
+def test_streamed_write_stall_over_a_full_backlog(monkeypatch, capfd, engine, bid):
+    """The write() of record 0 stalls until the reader has come to rest: 8
+    records fill the output ring, every wave holds a block, the reader is 8
+    blocks past the last claim; park, then the relaunch below the reader's
+    block.  Result 0 and exact bytes.  (MI355X: 0.5 - 0.9 s per case.)"""
+    _deep_env(monkeypatch)
+    st = {}
+    _deep_run(engine, bid, {}, {_record_write_call(engine, 0): _until_reader_rests(st)}, st)
+    _check_trace(capfd, "write()", 1)
+
+
+@pytest.mark.parametrize("engine,bid", _DEEP)
+def test_streamed_second_write_stall_after_a_relaunch(monkeypatch, capfd, engine, bid):
+    """The same stall at record 0 and again at record W // 2: the relaunched
+    grid, whose waves first pushed the blocks they parked with, backs up a
+    second time; both relaunches are below the reader's block.  (MI355X: 1.1 s
+    per case.)"""
+    _deep_env(monkeypatch)
+    W = _deep_case(bid)[0]
+    st = {}
+    hook = _until_reader_rests(st)
+    _deep_run(engine, bid, {}, {_record_write_call(engine, 0): hook, _record_write_call(engine, W // 2): hook}, st)
+    _check_trace(capfd, "write()", 2)
+
+
+@pytest.mark.parametrize("engine,bid", _DEEP)
+def test_streamed_read_stall_behind_a_slow_writer(monkeypatch, capfd, engine, bid):
+    """The writer is slow but below the park threshold (20 ms per write()), so
+    every wave backs up into its output wait; the read() of block
+    8 + W + 8 + 1 -- the compress's read() call 8 + W + 8 + 2; the decompress
+    takes three read() calls for the header and three per record, so the same
+    record's data is its call 5 + 3 (8 + W + 8 + 1) -- can only begin once all
+    that is so and two records are written, and sleeps 1 s: the park is
+    charged to the read() while the waves hold their blocks, and the relaunch
+    is below the reader's block.
+    Pacing while the read() sleeps: at full speed the writer would empty the
+    backlog in the 300 ms before the park (a record frees a slot, its wave
+    pushes and claims one of the 7 unclaimed blocks), the waves would be back
+    in their input waits and the device counter past the reader's; so the
+    writer stays slow, 120 ms per record (at most 3 of the 7 claimed before
+    the park, still below the park threshold per callback), until the read()
+    returns, and runs free after it.  (MI355X: 1.2 s per case.)"""
+    import time
+    _deep_env(monkeypatch)
+    W, N = _deep_case(bid)[:2]
+    begun, ended = [], []
+    per_record = 3 if engine == "compress" else 1   # write() calls
+
+    def stalled_read():
+        begun.append(1)
+        time.sleep(1.0)
+        ended.append(1)
+
+    def paced_write():
+        if not begun:
+            time.sleep(0.02)
+        elif not ended:
+            time.sleep(0.12 / per_record)
+
+    blk = _ROUT + W + _RIN + 1
+    call = blk + 1 if engine == "compress" else 5 + 3 * blk
+    _deep_run(engine, bid, {call: stalled_read}, {k: paced_write for k in range(1, 3 * N + 8)}, {})
+    assert begun and ended
+    _check_trace(capfd, "read()", 1)
