@@ -1114,313 +1114,65 @@ __device__ int32_t encode_block_v5(g_cu8* __restrict__ s, uint32_t n, g_u8* __re
     // carried as loop state (61 after every match) rather than recomputed
     uint32_t spanHi = 61;
     uint32_t nextSweep = 32768;   // P17
-    // ONE exit and no continue: the structurizer then needs no flow
-    // variables and the loop-carried state stays in place across windows
-    while (!done) {
-      // windows without a stop (continuations) loop here, inside: the
-      // match-path state (anchor, op, pe) is not touched by them
-      uint32_t w, ip, cd, maxb, cw, iw, bi, bc;
-      bool wTerm;
-      do {
-        if (ST) acc[10] += 1;
-        if (P17) {
-            while (sBase >= nextSweep) {   // (long matches cross several)
-                tab.sweep(nextSweep);
-                nextSweep += 32768;
-            }
-        }
-        // ---- probe positions.  SEARCH lane L probes k = k0 + j (j = L - 2) at
-        // sBase + j*s0 + max(0, j - j1): the step s0 = step(k0) rises by one at
-        // most once inside a window (at j = j1; never in the k0 = 0 window)
-        const uint32_t j = L - 2;
-        const int32_t jx = (int32_t)j - (int32_t)j1;
-        // j < 62 and the step s0 < 2^24: a full-rate 24-bit multiply (lanes 0
-        // and 1 wrap j, but take the INSERT / TEST position below)
-        uint32_t p = sBase + __umul24(j, s0) + (uint32_t)max(jx, 0);
-        const uint32_t step = s0 + (jx >= 0 ? 1u : 0u);
-        const uint32_t sHi = sBase + spanHi;
-        const bool insOn = mode != 0;
-        const uint32_t insPos = mode == 2 ? o0 : sBase - 3, testPos = sBase - 1;
-        p = L == 0 ? insPos : (L == 1 ? testPos : p);
-        // lane predicates as wave masks (SALU), turned back into per-lane
-        // conditions with inverse_ballot (the mask is the select's condition):
-        // no 0/1 materialisation chains.  Lane 0 / 1's bits come straight
-        // from the mode (2: INSERT only, 1: both, 0: neither)
-        const uint64_t roleM = (uint64_t)((0x130u >> (4 * mode)) & 3u);
-        const uint64_t liveM = (bal(p <= mflimitP1) & ~3ull) | roleM;
-        const uint64_t tmk = bal(p + step > mflimitP1) & liveM & ~3ull;
-        const bool live = __builtin_amdgcn_inverse_ballot_w64(liveM);
-        const bool term = __builtin_amdgcn_inverse_ballot_w64(tmk);
-        const uint32_t lo = insOn ? insPos : sBase;
-        const uint32_t hi = (sHi < mflimitP1 ? sHi : mflimitP1) + 8;
-        uint64_t v8;
-        // two if-regions and no else: the ring read is issued on both paths
-        // (wasted, harmless, in the rare wide case), so the common path
-        // carries no structurizer flow variable
-        const bool wide = hi - lo > 1024;
-        if constexpr (kPrioT) {   // the check rides on the ring's advance (every 512 B of input or more)
-            if (!wide && hi > V.B + kSR) {
-                const uint32_t oldB = V.B;
-                V.cover(hi);
-                if (prioOn && ((oldB ^ V.B) >> tickShift)) prio.tick(V.B - o0, blen);
-            }
+    // ---- two phases (the frame encoder's instantiation): general -> fast ->
+    // general.  The fast phase runs the same windows without the work whose
+    // result is fixed away from the block's end:
+    //   (a) end distance.  Every fast window starts at sBase <= fastEndS =
+    //       n - kFastEndGap with spanHi <= kFastSpanMax (so s0 <= 16), hence
+    //       for every lane p + step <= sBase + spanHi + 17 < mflimitP1
+    //       (liveM = ~3 | roleM, tmk = 0, wTerm false, hi = sHi + 8) and for
+    //       every stop ip + 4 + 4 kCountLanes + 8 <= matchlimit (no clamp of
+    //       the round trip's addresses or of the first count round binds).
+    //   (b) output safety.  With R = n - anchor the input still to encode,
+    //       fastEndS stays 0 until  op + R + R / 255 + kFastOutSlack <= cap.
+    //       A sequence (lit literals, match 4 + mcf) takes lit + 4 + mcf input
+    //       and 3 + litExt + lit + mlExt output, and litExt <= lit / 255 + 1,
+    //       mlExt <= mcf: cap - op - (R + R / 255) never falls, so the
+    //       condition, once true, holds at every later sequence.  There
+    //       1.9.3's three limitedOutput checks need at most lit + lit / 255 +
+    //       9 (before the literals), lit + litExt + 9 + (mcf + 240) / 255 <=
+    //       lit + mcf + lit / 255 + 11 (after the match length) and R +
+    //       R / 255 + 2 (last literals) bytes after op; R >= lit + mcf + 4,
+    //       so none can fire: the fast phase carries no margin test.
+    //   The wide window (hi - lo > 1024) needs spanHi > 1016: never in a fast
+    //   window.  The phase is left before a window that (a) or the span bound
+    //   does not cover: after a match by ipe >= fastEndS (in place of the
+    //   general ipe >= mflimitP1), after a continuation by the new sBase and
+    //   spanHi.  It is entered after a match only (spanHi = 61).
+    // LZ4MT_FAST_WINDOW (A/B builds): 0 the one general loop (also
+    // -DLZ4MT_NO_FAST_WINDOW); 1 the fast phase without the end predicates
+    // and clamps; + 2 without the margin test, entered once (b) holds;
+    // + 4 without the wide test
+#ifndef LZ4MT_FAST_WINDOW
+#ifdef LZ4MT_NO_FAST_WINDOW
+#define LZ4MT_FAST_WINDOW 0
+#else
+#define LZ4MT_FAST_WINDOW 7
+#endif
+#endif
+    constexpr bool kFastT = (LZ4MT_FAST_WINDOW & 1) && !ST && !U16 && !SPLIT && !LINK && !P17 && !PUB && !XH && !DUP;
+    constexpr bool kFastMargin = (LZ4MT_FAST_WINDOW & 2) != 0, kFastNoWide = (LZ4MT_FAST_WINDOW & 4) != 0;
+    constexpr uint32_t kFastSpanMax = 1016;   // hi - lo = spanHi + 8 <= 1024
+    // sBase + kFastSpanMax + 17 (step) + 4 + 4 kCountLanes + 8 < n - kMfLimit, with room to spare
+    constexpr uint32_t kFastEndGap = 1280;
+    static_assert(kFastSpanMax + 17 + 4 + 4 * kCountLanes + 8 + kMfLimit + 64 <= kFastEndGap, "fast phase end distance");
+    constexpr uint32_t kFastOutSlack = 64;
+    const uint32_t fastEndV = n > o0 + kFastEndGap ? n - kFastEndGap : 0u;
+    uint32_t fastEndS = (!kFastMargin || !limited) ? fastEndV : 0u;   // 0: (b) not established yet
+    // the window loop, once per phase (lz4mt_v5_window.inc: windows until the
+    // block is done or the phase changes); without a fast phase, one pass
+    for (;;) {
+#define V5_FAST false
+#include "lz4mt_v5_window.inc"
+#undef V5_FAST
+        if constexpr (kFastT) {
+            if (done) break;
+#define V5_FAST true
+#include "lz4mt_v5_window.inc"
+#undef V5_FAST
+            done = fail || anchor >= mflimitP1;   // (a match may have run up to the block's end)
         } else {
-            if (!wide) V.cover(hi);
-        }
-        v8 = V.rd8(p);
-        if (wide) {   // wide window (long searches): hash inputs straight from global
-            if (ST) acc[13] += 1;
-            v8 = gld8u(s + (p < n - 8 ? p : n - 8));
-            uint32_t a = (uint32_t)v8, b = (uint32_t)(v8 >> 32);
-            asm volatile("" : "+v"(a), "+v"(b));   // land it here, not at the join
-            v8 = ((uint64_t)b << 32) | a;
-        }
-        const uint32_t w0 = (uint32_t)v8;
-        uint32_t h, tg;
-        if constexpr (G::HT && U16) {   // one product: hash4 = bits 19..31, tag = the TB bits below
-            const uint32_t P = w0 * 2654435761u;
-            h = P >> 19;
-            tg = (P >> (19 - G::TB)) & ((1u << G::TB) - 1u);
-        } else if constexpr (G::HT) {   // one product: hash5 = bits 52..63, tag = the TB bits below
-            const uint64_t P = (v8 << 24) * 889523592379ull;
-            h = (uint32_t)(P >> 52);
-            tg = (uint32_t)(P >> (52 - G::TB)) & ((1u << G::TB) - 1u);
-        } else {
-            h = lz4_hash<U16>(w0, (uint32_t)(v8 >> 32));
-            tg = G::tag(w0);
-        }
-        const uint32_t mark = (P17 ? p & G::PM : p) | (tg << G::PB);   // the lane's final table entry
-        // ---- table probe: read, write the marker, read back (LDS ops of a wave run in order)
-        const uint32_t ti = live ? h : dumIdx;
-        uint32_t told;
-        uint64_t pend = 0;   // same-bucket collisions inside the window (XCHG: none to resolve)
-        if constexpr (XCHG) {
-            told = tab.xchg(ti, mark);
-        } else {
-            told = tab.ld(ti);
-            tab.st(ti, mark);
-            WAVE_SYNC();
-            const uint32_t sv = tab.rb(ti);
-            pend = bal(sv != (mark & G::kRbMask));
-        }
-        const uint32_t dq = (p - told) & G::PM;   // P17: the distance, exact below 2^17
-        uint32_t cand = P17 ? p - dq : told & G::PM;
-        const uint64_t cokM = bal((P17 ? dq <= kDistMax : cand + kDistMax >= p) && (!LINK || cand >= lk.candLow)) &
-                              liveM & ~tmk & ~1ull;
-        uint64_t mm = cokM & bal((told >> G::PB) == (mark >> G::PB));
-        bool maybe = __builtin_amdgcn_inverse_ballot_w64(mm);
-        uint64_t sm = mm | tmk;
-        STAMP_ADD(0, ts);
-        // ---- resolve the first stop.  Exact in-window predecessors are
-        // resolved (once) whenever a collision reaches the current stop
-        // candidate -- also after a tag alias moved the stop further out.
-        // The round trip: verify word + forward count words, catch-up bytes;
-        // the previous sequence's stores go out behind them.
-        w = 64;
-        bool dd = false, twDone = false, twRedo = false;
-        uint64_t gmask, aliased = 0;   // gmask: read only after dd set it
-        // table writes for stop w: lanes past the stop put the old entry
-        // back; on a collision (or when redone after a tag alias moved the
-        // stop) the lanes up to the stop re-insert (last member of each group)
-        // pB: the position of lane wlim (the last lane whose insert stays)
-        auto table_writes = [&](uint32_t ws, bool wsTerm, uint32_t pB) {
-            // (an SGPR-pinned version of this, w - ((tmk >> w) & 1) under an
-            // asm "+s" constraint, drops a v_readfirstlane but costs 1 ms:
-            // profiles/r04tidy_encoder_ab.txt)
-            const int wlim = (ws == 64) ? 63 : (wsTerm ? (int)ws - 1 : (int)ws);
-            const bool le = (int)L <= wlim;
-            if constexpr (XCHG) {
-                // after an alias moved the stop: the lanes up to it insert again
-                // (exchanges, so the last of each bucket wins)
-                if (twRedo) (void)tab.xchg((live && le) ? h : dumIdx, mark);
-                // lanes past the stop: the first of each bucket puts back the
-                // entry it displaced (the last mark up to the stop, or the
-                // table's entry); a later one displaced a lane past the stop.
-                // Lanes are in position order and every entry a lane can
-                // displace is an older table entry or an earlier lane's
-                // mark, so "displaced by no lane past the stop" is "its
-                // position is at most lane wlim's" (P17 keeps positions
-                // mod 2^17: compare distances from p)
-                const bool first = P17 ? dq >= p - pB : (told & G::PM) <= pB;
-                tab.st((live && !le && first) ? h : dumIdx, told);
-            } else {
-                tab.st((live && !le) ? h : dumIdx, told);
-                if (pend || twRedo) {
-                    const uint64_t upto = wlim < 0 ? 0ull : mask_le((uint32_t)wlim);
-                    const bool lastM = !dd || !(gmask & ~mask_le(L) & upto);
-                    tab.st((live && le && lastM) ? h : dumIdx, mark);
-                }
-            }
-            WAVE_SYNC();
-        };
-        // ip .. bc and wTerm are set on the path that reads them (a stop
-        // inside the window): no per-window zeroing
-        bool again = true;
-        while (again) {
-            w = sff1(sm);
-            if (!dd && (pend & mask_le(w < 63 ? w : 63))) {
-                if (ST) acc[12] += 1;
-                dd = true;
-                int pred = -1;
-                gmask = 1ull << L;
-                uint64_t todo = pend;
-                while (todo) {   // one iteration per group of equal hashes
-                    const uint32_t key = rdlane(h, (int)sff1(todo));
-                    const uint64_t m = bal(live && h == key);
-                    const bool inG = (m >> L) & 1;
-                    const uint64_t below = m & ((1ull << L) - 1ull);
-                    pred = inG ? (below ? 63 - __clzll((long long)below) : -1) : pred;
-                    gmask = inG ? m : gmask;
-                    todo &= ~m;
-                }
-                const int pi = (pred < 0 ? 0 : pred) * 4;
-                const uint32_t pw = (uint32_t)__builtin_amdgcn_ds_bpermute(pi, (int)w0);   // predecessor's bytes
-                const uint32_t pp = (uint32_t)__builtin_amdgcn_ds_bpermute(pi, (int)p);    // and position
-                const bool ok = live && L != 0 && !term && pred >= 0 && pp + kDistMax >= p && pw == w0 &&
-                                (!LINK || pp >= lk.candLow);
-                maybe = maybe && pred < 0;
-                cand = pred >= 0 ? pp : cand;
-                mm = bal(maybe);
-                sm = (bal(ok) | mm | tmk) & ~aliased;
-            } else {
-                wTerm = w < 64 && ((tmk >> w) & 1);
-                again = false;
-                if (w < 64 && !wTerm) {
-                    ip = rdlane(p, (int)w);
-                    cd = rdlane(cand, (int)w);
-                    {   // catch-up bound: lz4's lowLimit for the candidate's side
-                        const uint32_t lowL = !LINK ? 0u : (cd >= o0 ? lk.lowIn : lk.lowDict);
-                        maxb = w == 1 ? 0u : min(ip - anchor, cd > lowL ? cd - lowL : 0u);
-                    }
-                    // lane 0: verify word; lanes 1 .. kCountLanes: count words; the
-                    // rest repeat lane 0's address (no further lines touched)
-                    const bool cOn = L <= kCountLanes;
-                    const uint32_t ci = cOn ? cd + 4 * L : cd, ii = cOn ? ip + 4 * L : ip;
-                    const bool bOn = L < maxb && L < kCatchLanes;
-                    // every side from global memory: reading the near side(s)
-                    // from the LDS ring when they lie in it was slower
-                    // (profiles/r03j_encoder_ring_rt_ab.txt, r04s_encoder_ip_ring_ab.txt)
-                    cw = xld4(ci < last4 ? ci : last4);
-                    iw = gld4u(s + (ii < last4 ? ii : last4));
-                    uint32_t bix = bOn ? ip - L - 1 : o0, bcx = bOn ? cd - L - 1 : o0;   // (o0: a byte of the block itself)
-                    asm volatile("" : "+v"(bix), "+v"(bcx));   // 32-bit offsets, SGPR-base loads
-                    bi = s[bix];
-                    bc = xld1(bcx);
-                    if (havePe) store_pending();
-                    table_writes(w, false, ip);   // in the round trip's shadow; redone if w moves
-                    twDone = true;
-                    if (((mm >> w) & 1) && rdlane(cw, 0) != rdlane(w0, (int)w)) {   // tag alias: no match here
-                        if (ST) acc[11] += 1;
-                        // drain this try's loads here, so the loop head's load
-                        // registers carry nothing pending into the common path
-                        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-                        aliased |= 1ull << w;
-                        sm &= ~(1ull << w);
-                        again = true;
-                        twDone = false;
-                        twRedo = true;
-                    }
-                }
-            }
-        }
-        if (havePe) store_pending();
-        // no stop in the window (w == 64): every insert stays, nothing to put
-        // back -- unless an alias moved the stop here after the lanes past the
-        // old one were put back (twRedo: they insert again)
-        if (!twDone && (!XCHG || w < 64 || twRedo)) table_writes(w, wTerm, rdlane(p, (int)(w < 64 ? w - 1 : 63)));
-        STAMP_ADD(1, ts);
-        STAMP_ADD(2, ts);
-        if (w == 64) {   // no stop: the search goes on
-            sBase += 62 * s0 + (62 > j1 ? 62 - j1 : 0u);
-            k0 += 62;
-            s0 = (63 + k0) >> 6;   // k0 >= 62: no max(1, .) needed
-            j1 = (k0 < 65 ? 65u : ((k0 - 1) & ~63u) + 65) - k0;
-            mode = 0;
-            spanHi = 61 * s0 + (61 > j1 ? 61 - j1 : 0u);
-        }
-      } while (w == 64);
-        if (wTerm) {
-            done = true;
-        } else {
-            // ---- catch-up (backwards) and LZ4_count (forwards from ip + 4).
-            // bi/bc are consumed on every path, so no load of this window is
-            // left pending into the next window's round trip.
-            asm volatile("" ::"v"(bi), "v"(bc));
-            uint64_t fm = ~(bal(L < maxb) & bal(bi == bc)) & kCatchMask;
-            uint32_t back = 0;
-            if (kCatchLanes < 64 && fm == 0) {   // every loaded byte matched, the limit lies beyond them
-                back = kCatchLanes;
-                const uint32_t kb = back + L + 1;
-                const bool on = kb <= maxb;
-                fm = ~bal(on && s[on ? ip - kb : o0] == xld1(on ? cd - kb : o0));
-            }
-            while (fm == 0 && back + 64 < maxb) {   // catch-up longer than 64 bytes
-                back += 64;
-                const uint32_t kb = back + L + 1;
-                const bool on = kb <= maxb;
-                fm = ~bal(on && s[on ? ip - kb : o0] == xld1(on ? cd - kb : o0));
-            }
-            back = fm ? back + (uint32_t)__builtin_ctzll(fm) : maxb;
-            const uint32_t lim = matchlimit - (ip + kMinMatch);
-            uint32_t mc;
-            {
-                const uint32_t rel = 4 * L - 4;
-                const uint32_t x = cw ^ iw;
-                uint32_t e = min(x ? ((uint32_t)__builtin_ctz(x) >> 3) : 4u, lim - rel);
-                e = rel < lim ? e : 0u;   // (lane 0's e is masked out below)
-                const uint64_t nf = bal(e < 4) & (mask_le(kCountLanes) & ~1ull);
-                if (nf) {
-                    const uint32_t f = (uint32_t)__builtin_ctzll(nf);
-                    mc = 4 * (f - 1) + rdlane(e, (int)f);
-                } else {
-                    mc = 4 * kCountLanes;
-                    uint64_t nf2 = 0;
-                    while (!nf2) {   // long match: 256 bytes per round
-                        const uint32_t r2 = mc + 4 * L;
-                        const uint32_t a2 = ip + kMinMatch + r2, c2 = cd + kMinMatch + r2;
-                        const uint32_t x2 = gld4u(s + (a2 < last4 ? a2 : last4)) ^ xld4(c2 < last4 ? c2 : last4);
-                        uint32_t e2 = min(x2 ? ((uint32_t)__builtin_ctz(x2) >> 3) : 4u, lim - r2);
-                        e2 = r2 < lim ? e2 : 0u;
-                        nf2 = bal(e2 < 4);
-                        mc += nf2 ? 4 * (uint32_t)__builtin_ctzll(nf2) + rdlane(e2, (int)__builtin_ctzll(nf2))
-                                  : 256u;
-                    }
-                }
-            }
-            STAMP_ADD(3, ts);
-            // ---- sequence layout (stored during the next round trip)
-            const uint32_t lit = ip - anchor - back, mcf = mc + back;
-            pe.lit = lit;
-            pe.mcf = mcf;
-            pe.off = ip - cd;
-            pe.anchor = anchor;
-            {
-                const uint32_t litExt = ext_len(lit), mlExt = ext_len(mcf);
-                pe.litExt = litExt;
-                pe.mlExt = mlExt;
-                // 1.9.3's limitedOutput margins; both hold whenever
-                // op + 2 (lit + mcf) + 16 <= cap, so the exact test runs rarely
-                if (op + 2 * (lit + mcf) + 16 > capL) {
-                    fail = (w != 1 && op + 1 + lit + 8 + lit / 255 > cap) ||
-                           (op + 1 + litExt + lit + 2 + 6 + (mcf + 240) / 255 > cap);
-                }
-                pe.op = op;
-                havePe = !fail;
-                if constexpr (PUB) {   // every sequence before this one has been stored: [0, op) is final
-                    if ((op ^ (op + 1 + litExt + lit + 2 + mlExt)) >> kPubShift) publish_progress(pub, op);
-                }
-                op += 1 + litExt + lit + 2 + mlExt;
-            }
-            const uint32_t ipe = ip + kMinMatch + mc;
-            anchor = ipe;
-            done = fail || ipe >= mflimitP1;
-            mode = 1;
-            sBase = ipe + 1;
-            k0 = 0;
-            s0 = 1;
-            j1 = 65;
-            spanHi = 61;
-            STAMP_ADD(4, ts);
+            break;
         }
     }
     if (prioOn) prio.done();

@@ -185,11 +185,29 @@ def tag_ht(w0):
     return ((((w0 << 24) * 889523592379) & 0xFFFFFFFFFFFFFFFF) >> (52 - (32 - POSB))) & ((1 << (32 - POSB)) - 1)
 
 
-def encode_xchg(s, cap):
+FAST_SPAN_MAX = 1016   # encode_block_v5: kFastSpanMax, kFastEndGap, kFastOutSlack, kCountLanes
+FAST_END_GAP = 1280
+FAST_OUT_SLACK = 64
+COUNT_LANES = 32
+
+
+def encode_xchg(s, cap, phases=None):
+    """phases (a dict, optional): also runs encode_block_v5's phase rules
+    (general -> fast -> general) beside the parse and asserts, at every
+    window of the fast phase, that what the kernel's fast body drops has the
+    value it assumes: every SEARCH lane live, none terminating, no clamp of
+    hi, of the round trip's addresses or of the first count round binding,
+    no wide window, neither margin test firing.  Counts the windows and
+    phase entries into it."""
     n = len(s)
+    fast = False
+    fast_end_v = n - FAST_END_GAP if n > FAST_END_GAP else 0
     assert 65547 <= n <= 1 << 22
     bound = n + n // 255 + 16
     limited = cap < bound
+    fast_end_s = 0 if limited else fast_end_v   # 0: output safety (b) not established yet
+    if phases is not None:
+        phases.update(fast_windows=0, general_windows=0, entries=0, wide_general=0)
     T = [(tag_ht(rd32(s, 0)) << POSB)] * 4096 + [0] * 64
     mfl = n - 12 + 1
     matchlimit = n - 5
@@ -207,6 +225,16 @@ def encode_xchg(s, cap):
         p[1] = sPos - 1
         live = [p[L] <= mfl if L >= 2 else (mode != 0 if L == 0 else mode == 1) for L in range(64)]
         term = [L >= 2 and live[L] and p[L] + step[L] > mfl for L in range(64)]
+        if phases is not None:
+            lo = p[0] if mode != 0 else p[2]
+            if fast:
+                phases["fast_windows"] += 1
+                assert all(live[2:]) and not any(term), (sPos, k0)
+                assert p[63] < mfl and p[63] + 8 - lo <= 1024, (sPos, k0)
+                assert p[2] <= fast_end_s and p[63] - p[2] <= FAST_SPAN_MAX, (sPos, k0)
+            else:
+                phases["general_windows"] += 1
+                phases["wide_general"] += min(p[63], mfl) + 8 - lo > 1024
         w0 = [rd32(s, min(p[L], n - 8)) for L in range(64)]
         h = [h5(rd64(s, min(p[L], n - 8))) for L in range(64)]
         mark = [(p[L] | (tag_ht(w0[L]) << POSB)) & 0xFFFFFFFF for L in range(64)]
@@ -250,10 +278,15 @@ def encode_xchg(s, cap):
         if w == 64:   # (probe offsets poff(k) count from the sequence's first search position)
             k0 += 62
             mode = 0
+            if fast:   # the next window's first position and span decide
+                nb, nspan = sPos + poff(k0), poff(k0 + 61) - poff(k0)
+                fast = not (nspan > FAST_SPAN_MAX or nb > fast_end_s)
             continue
         if wTerm:
             break
         ip, cd = p[w], cand[w]
+        if fast:   # the round trip's loads and the first count round need no clamp
+            assert ip + 4 * COUNT_LANES < n - 4 and matchlimit - (ip + 4) >= 4 * COUNT_LANES, ip
         maxb = 0 if w == 1 else min(ip - anchor, cd)
         back = 0
         while back < maxb and s[ip - back - 1] == s[cd - back - 1]:
@@ -266,9 +299,10 @@ def encode_xchg(s, cap):
         mcf = mc + back
         litExt, mlExt = ext_len(lit), ext_len(mcf)
         if limited:
-            if w != 1 and op + 1 + lit + 8 + lit // 255 > cap:
-                return b""
-            if op + 1 + litExt + lit + 2 + 6 + (mcf + 240) // 255 > cap:
+            fails = (w != 1 and op + 1 + lit + 8 + lit // 255 > cap) or \
+                op + 1 + litExt + lit + 2 + 6 + (mcf + 240) // 255 > cap
+            assert not (fast and fails), (ip, op)   # the fast body has no margin test
+            if fails:
                 return b""
         tok = (min(lit, 15) << 4) | min(mcf, 15)
         seq = bytearray([tok])
@@ -283,12 +317,21 @@ def encode_xchg(s, cap):
         op += len(seq)
         ipe = ip + 4 + mc
         anchor = ipe
+        if fast:
+            fast = ipe < fast_end_s
+        else:
+            if fast_end_s == 0 and op + (n - ipe) + (n - ipe) // 255 + FAST_OUT_SLACK <= cap:
+                fast_end_s = fast_end_v
+            fast = ipe < fast_end_s
+            if fast and phases is not None:
+                phases["entries"] += 1
         if ipe >= mfl:
             break
         mode = 1
         sPos, k0 = ipe + 1, 0
     run = n - anchor
     if limited and op + run + 1 + (run + 240) // 255 > cap:
+        assert fast_end_s == 0, (anchor, op)   # (b) covers the last literals too
         return b""
     out.append(min(run, 15) << 4)
     if run >= 15:
