@@ -1142,16 +1142,25 @@ __device__ int32_t encode_block_v5(g_cu8* __restrict__ s, uint32_t n, g_u8* __re
     // LZ4MT_FAST_WINDOW (A/B builds): 0 the one general loop (also
     // -DLZ4MT_NO_FAST_WINDOW); 1 the fast phase without the end predicates
     // and clamps; + 2 without the margin test, entered once (b) holds;
-    // + 4 without the wide test
+    // + 4 without the wide test; + 8 first windows only: the fast body runs
+    // the first window after a match with its window state (k0 = 0, s0 = 1,
+    // j1 = 65, mode = 1, spanHi = 61) folded into constants, and a window
+    // without a stop leaves the phase: the general body resumes the search
+    // from the continuation state (k0 = 62) and the phase is entered again
+    // after its match.  Without bit 8 the loop is the one of bits 1 + 2 + 4.
 #ifndef LZ4MT_FAST_WINDOW
 #ifdef LZ4MT_NO_FAST_WINDOW
 #define LZ4MT_FAST_WINDOW 0
 #else
-#define LZ4MT_FAST_WINDOW 7
+#define LZ4MT_FAST_WINDOW 15
 #endif
 #endif
     constexpr bool kFastT = (LZ4MT_FAST_WINDOW & 1) && !ST && !U16 && !SPLIT && !LINK && !P17 && !PUB && !XH && !DUP;
     constexpr bool kFastMargin = (LZ4MT_FAST_WINDOW & 2) != 0, kFastNoWide = (LZ4MT_FAST_WINDOW & 4) != 0;
+    constexpr bool kFastFirst = (LZ4MT_FAST_WINDOW & 8) != 0;
+    // first window after a match: lane L's position minus sBase (INSERT
+    // sBase - 3, TEST sBase - 1, SEARCH sBase + L - 2)
+    const uint32_t firstOff = L == 0 ? (uint32_t)-3 : (L == 1 ? (uint32_t)-1 : L - 2);
     constexpr uint32_t kFastSpanMax = 1016;   // hi - lo = spanHi + 8 <= 1024
     // sBase + kFastSpanMax + 17 (step) + 4 + 4 kCountLanes + 8 < n - kMfLimit, with room to spare
     constexpr uint32_t kFastEndGap = 1280;

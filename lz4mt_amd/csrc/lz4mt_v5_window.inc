@@ -4,9 +4,15 @@
 // lambda or a helper template: the instantiations without a fast phase
 // then compile to the code they had as one loop, and the loop-carried state
 // stays in the enclosing function's registers.
+// FIRST (the fast body under LZ4MT_FAST_WINDOW bit 8): every window of the
+// phase is the first window after a match, so k0 = 0, s0 = 1, j1 = 65,
+// mode = 1 and spanHi = 61 are constants here and not loop state; a window
+// without a stop leaves the phase with the continuation state written out.
 {
     constexpr bool FAST = V5_FAST;
+    constexpr bool FIRST = FAST && kFastFirst;
     bool sw = false;   // leave this phase
+    bool fcont = false;   // FIRST: the phase was left by a window without a stop
     // ONE exit and no continue: the structurizer then needs no flow
     // variables and the loop-carried state stays in place across windows
     while (!done && !sw) {
@@ -30,20 +36,23 @@
         // j < 62 and the step s0 < 2^24: a full-rate 24-bit multiply (lanes 0
         // and 1 wrap j, but take the INSERT / TEST position below)
         uint32_t p = sBase + __umul24(j, s0) + (uint32_t)max(jx, 0);
-        const uint32_t step = s0 + (jx >= 0 ? 1u : 0u);
-        const uint32_t sHi = sBase + spanHi;
-        const bool insOn = mode != 0;
-        const uint32_t insPos = mode == 2 ? o0 : sBase - 3, testPos = sBase - 1;
+        const uint32_t step = FIRST ? 1u : s0 + (jx >= 0 ? 1u : 0u);
+        const uint32_t sHi = sBase + (FIRST ? 61u : spanHi);
+        const bool insOn = FIRST ? true : mode != 0;
+        const uint32_t insPos = !FIRST && mode == 2 ? o0 : sBase - 3, testPos = sBase - 1;
         p = L == 0 ? insPos : (L == 1 ? testPos : p);
+        // (FIRST, j1 = 65 > j and s0 = 1: all of the above is one add of the
+        // lane's constant offset, -3, -1 or L - 2)
+        if constexpr (FIRST) p = sBase + firstOff;
         // lane predicates as wave masks (SALU), turned back into per-lane
         // conditions with inverse_ballot (the mask is the select's condition):
         // no 0/1 materialisation chains.  Lane 0 / 1's bits come straight
         // from the mode (2: INSERT only, 1: both, 0: neither)
-        const uint64_t roleM = (uint64_t)((0x130u >> (4 * mode)) & 3u);
+        const uint64_t roleM = FIRST ? 3ull : (uint64_t)((0x130u >> (4 * mode)) & 3u);
         // (fast phase: every SEARCH lane is live and none is the block's last)
         const uint64_t liveM = FAST ? ~3ull | roleM : (bal(p <= mflimitP1) & ~3ull) | roleM;
         const uint64_t tmk = FAST ? 0ull : bal(p + step > mflimitP1) & liveM & ~3ull;
-        const bool live = __builtin_amdgcn_inverse_ballot_w64(liveM);
+        const bool live = FIRST ? true : __builtin_amdgcn_inverse_ballot_w64(liveM);
         const bool term = FAST ? false : __builtin_amdgcn_inverse_ballot_w64(tmk);
         const uint32_t lo = insOn ? insPos : sBase;
         const uint32_t hi = (FAST || sHi < mflimitP1 ? sHi : mflimitP1) + 8;
@@ -226,7 +235,15 @@
         if (!twDone && (!XCHG || w < 64 || twRedo)) table_writes(w, wTerm, rdlane(p, (int)(w < 64 ? w - 1 : 63)));
         STAMP_ADD(1, ts);
         STAMP_ADD(2, ts);
-        if (w == 64) {   // no stop: the search goes on
+        if constexpr (FIRST) {
+            // no stop: the search goes on in the general body, which resumes
+            // it from the continuation state written behind this loop
+            if (w == 64) {
+                sBase += 62;
+                fcont = true;
+                sw = true;
+            }
+        } else if (w == 64) {   // no stop: the search goes on
             sBase += 62 * s0 + (62 > j1 ? 62 - j1 : 0u);
             k0 += 62;
             s0 = (63 + k0) >> 6;   // k0 >= 62: no max(1, .) needed
@@ -237,7 +254,7 @@
             // is a continuation: the test is off the sequence chain)
             if constexpr (FAST) sw = spanHi > kFastSpanMax || sBase > fastEndS;
         }
-      } while (w == 64 && !(FAST && sw));
+      } while (!FIRST && w == 64 && !(FAST && sw));
         if (FAST && w == 64) {
             // phase left inside a search: the general loop resumes it
         } else if (wTerm) {
@@ -333,13 +350,25 @@
                     sw = !fail && ipe < fastEndS;   // (fastEndS < mflimitP1)
                 }
             }
-            mode = 1;
             sBase = ipe + 1;
-            k0 = 0;
-            s0 = 1;
-            j1 = 65;
-            spanHi = 61;
+            if constexpr (!FIRST) {
+                mode = 1;
+                k0 = 0;
+                s0 = 1;
+                j1 = 65;
+                spanHi = 61;
+            }
             STAMP_ADD(4, ts);
         }
+    }
+    // FIRST: the window state the general body resumes from, written once per
+    // phase change and not per sequence -- the second window of a search
+    // (k0 = 62: the step rises at j = 3), or the first window after a match
+    if constexpr (FIRST) {
+        k0 = fcont ? 62u : 0u;
+        j1 = fcont ? 3u : 65u;
+        mode = fcont ? 0u : 1u;
+        spanHi = fcont ? 119u : 61u;
+        s0 = 1;
     }
 }

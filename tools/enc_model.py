@@ -198,7 +198,20 @@ def encode_xchg(s, cap, phases=None):
     value it assumes: every SEARCH lane live, none terminating, no clamp of
     hi, of the round trip's addresses or of the first count round binding,
     no wide window, neither margin test firing.  Counts the windows and
-    phase entries into it."""
+    phase entries into it.
+    A fast window is a first window after a match (LZ4MT_FAST_WINDOW bit 8):
+    the kernel's fast body folds the window state k0 = 0, s0 = 1, j1 = 65,
+    mode = 1, spanHi = 61 into constants, and a window without a stop leaves
+    the phase with the continuation state written as constants.  The model
+    carries the kernel's window state (sBase, k0, s0, j1, spanHi) beside its
+    own and asserts at every fast window that the folded values -- lane
+    positions sBase + c(L), roleM = 3, every lane live, lo = sBase - 3,
+    hi = sBase + 69, step 1, and the continuation state at a no-stop exit --
+    equal the general formulas.  Also counted: fast_stop_lanes[L] (stops per
+    lane in fast windows), cont1_stop_lanes[L] (stops per lane in the first
+    continuation window after a fast exit), fast_exits_redo (fast windows
+    left without a stop after a tag alias, the exit that redoes the table
+    writes)."""
     n = len(s)
     fast = False
     fast_end_v = n - FAST_END_GAP if n > FAST_END_GAP else 0
@@ -207,7 +220,10 @@ def encode_xchg(s, cap, phases=None):
     limited = cap < bound
     fast_end_s = 0 if limited else fast_end_v   # 0: output safety (b) not established yet
     if phases is not None:
-        phases.update(fast_windows=0, general_windows=0, entries=0, wide_general=0)
+        phases.update(fast_windows=0, general_windows=0, entries=0, wide_general=0,
+                      fast_stop_lanes=[0] * 64, cont1_stop_lanes=[0] * 64, fast_exits_redo=0)
+    j1, span_hi = 65, 61   # the kernel's window state beside sPos + poff(k0), k0 and s0 = step(k0)
+    after_fast_exit = False   # this window is the first continuation window after a fast exit
     T = [(tag_ht(rd32(s, 0)) << POSB)] * 4096 + [0] * 64
     mfl = n - 12 + 1
     matchlimit = n - 5
@@ -227,8 +243,20 @@ def encode_xchg(s, cap, phases=None):
         term = [L >= 2 and live[L] and p[L] + step[L] > mfl for L in range(64)]
         if phases is not None:
             lo = p[0] if mode != 0 else p[2]
+            # the kernel's general formulas on its own window state
+            sBase, s0 = sPos + poff(k0), max(1, (63 + k0) >> 6)
+            assert span_hi == p[63] - p[2], (sPos, k0)
+            for L in range(2, 64):
+                assert p[L] == sBase + (L - 2) * s0 + max(0, L - 2 - j1), (sPos, k0, L)
+                assert step[L] == s0 + (L - 2 >= j1), (sPos, k0, L)
             if fast:
                 phases["fast_windows"] += 1
+                # the folded values of the first window equal the general ones
+                assert (mode, k0, s0, j1, span_hi) == (1, 0, 1, 65, 61), (sPos, mode, k0)
+                assert p == [sBase + (-3 if L == 0 else -1 if L == 1 else L - 2) for L in range(64)], sPos
+                assert (0x130 >> (4 * mode)) & 3 == 3 and all(live), sPos   # roleM, liveM
+                assert step == [1] * 64, sPos
+                assert lo == sBase - 3 and min(sBase + span_hi, mfl) + 8 == sBase + 69, sPos
                 assert all(live[2:]) and not any(term), (sPos, k0)
                 assert p[63] < mfl and p[63] + 8 - lo <= 1024, (sPos, k0)
                 assert p[2] <= fast_end_s and p[63] - p[2] <= FAST_SPAN_MAX, (sPos, k0)
@@ -275,12 +303,27 @@ def encode_xchg(s, cap, phases=None):
             break
         wlim = 63 if w == 64 else (w - 1 if wTerm else w)
         table_writes(wlim)
+        if phases is not None and w < 64 and not wTerm:
+            if fast:
+                phases["fast_stop_lanes"][w] += 1
+            elif after_fast_exit:
+                phases["cont1_stop_lanes"][w] += 1
+        after_fast_exit = False
         if w == 64:   # (probe offsets poff(k) count from the sequence's first search position)
+            # the kernel's foot: the next window's state from this one's
+            nb = sPos + poff(k0) + 62 * max(1, (63 + k0) >> 6) + max(0, 62 - j1)
             k0 += 62
             mode = 0
-            if fast:   # the next window's first position and span decide
-                nb, nspan = sPos + poff(k0), poff(k0 + 61) - poff(k0)
-                fast = not (nspan > FAST_SPAN_MAX or nb > fast_end_s)
+            s0 = (63 + k0) >> 6
+            j1 = (65 if k0 < 65 else ((k0 - 1) & ~63) + 65) - k0
+            span_hi = 61 * s0 + max(0, 61 - j1)
+            assert nb == sPos + poff(k0), (sPos, k0)
+            if fast:   # a fast window without a stop leaves the phase: the state it writes as constants
+                assert (nb, k0, s0, j1, mode, span_hi) == (sPos + 62, 62, 1, 3, 0, 119), (sPos, k0)
+                if phases is not None:
+                    phases["fast_exits_redo"] += redo
+                fast = False
+                after_fast_exit = True
             continue
         if wTerm:
             break
@@ -329,6 +372,7 @@ def encode_xchg(s, cap, phases=None):
             break
         mode = 1
         sPos, k0 = ipe + 1, 0
+        j1, span_hi = 65, 61
     run = n - anchor
     if limited and op + run + 1 + (run + 240) // 255 > cap:
         assert fast_end_s == 0, (anchor, op)   # (b) covers the last literals too
@@ -338,6 +382,34 @@ def encode_xchg(s, cap, phases=None):
         out += b"\xff" * (ext_len(run) - 1) + bytes([(run - 15) % 255])
     out += s[anchor:]
     return bytes(out)
+
+
+def literal_run_sweep(n, seed):
+    """Inputs for the first-window fast phase: units of r fresh random bytes
+    followed by a copy of 8..40 earlier bytes from within 60 KB, r cycling
+    through 0..199.  After the match that ends a unit the next search stops
+    r positions on: at every SEARCH lane of the first window, on the TEST
+    lane (r = 0, back-to-back matches) and, past 62 literals, at the lanes of
+    the first and second continuation windows (the step rises inside the
+    first one, at j1 = 3)."""
+    rnd = random.Random(seed)
+    out = bytearray(oracle.gen_random(4096, seed))
+    r = 0
+    while len(out) < n:
+        out += oracle.gen_random(r, rnd.randrange(1 << 30)) if r else b""
+        k = rnd.randrange(8, 41)
+        a = rnd.randrange(max(0, len(out) - 60_000), len(out) - k)
+        out += out[a:a + k]
+        r = (r + 1) % 200
+    return bytes(out[:n])
+
+
+def long_search_input(n, run, seed):
+    """a compressible prefix, `run` random bytes (one search that leaves the
+    fast phase and ends in the general one), a compressible suffix"""
+    syn = oracle.gen_synthetic(n, seed)
+    prefix = min(40_000, n // 4)
+    return (syn[:prefix] + oracle.gen_random(run, seed + 1) + syn[prefix:])[:n]
 
 
 def fuzz_cases():
