@@ -215,7 +215,52 @@ int lz4mtHipCopyAsync(void* d_dst, const void* d_src, uint64_t n, void* stream);
  * stream; UINT64_MAX on bad arguments or a device error. */
 uint64_t lz4mtHipShardBodyBytes(uint64_t n, const Lz4MtStreamDescriptor* sd, void* d_ws, uint64_t wsSize, void* stream);
 
-/* ---- 5. diagnostics ----------------------------------------------------- */
+/* ---- 5. batched block operators (device memory) ------------------------- */
+/* Many independent raw LZ4 blocks ("chunks") that already live in HBM, one
+ * launch per call, one wavefront per chunk.  Chunk i is d_srcPtrs[i]
+ * [0, d_srcSizes[i]) and goes to d_dstPtrs[i] [0, d_dstCaps[i]); its outcome
+ * is d_outSizes[i].
+ * All pointers are device pointers; `stream` is a hipStream_t as void*.
+ * Asynchronous: no host synchronisation, no allocation, no host read of the
+ * arrays -- so both calls can be captured into a HIP graph (a compress call
+ * captured before any uncaptured call has checked the device's encoder
+ * order takes the read-back probe, as the frame engine does: same bytes).
+ *
+ * Compress (the fast codec, level 0): bytes and d_outSizes[i] are those of
+ * lz4mtHipCompressBlock(src, dst, d_srcSizes[i], d_dstCaps[i], 0), i.e.
+ * LZ4_compress_limitedOutput of lz4 1.9.3 -- 0 when the block does not fit.
+ * d_dstCaps == NULL: every capacity is lz4mtHipCompressBound(d_srcSizes[i]).
+ * A size of 0 is valid (the one-token block).  maxChunkBytes is the caller's
+ * promise d_srcSizes[i] <= maxChunkBytes <= LZ4MT_HIP_BATCH_MAX_CHUNK; it
+ * selects the kernel (below 65 547: the byU16-only one).
+ * Decompress: bytes and d_outSizes[i] are those of
+ * lz4mtHipDecompressBlock(src, dst, d_srcSizes[i], d_dstCaps[i]), i.e.
+ * LZ4_decompress_safe -- negative for a malformed block.  d_dstCaps[i] may
+ * be anything from 0 up (a size or capacity above INT32_MAX gives -1, that
+ * call's answer to a negative int); bytes of dst past the returned size are
+ * unspecified.
+ *
+ * Memory: sources at any alignment, a chunk may end on the last byte of its
+ * allocation (no source dword outside the chunk is read); destinations
+ * 16-byte aligned; nothing is written at or beyond dst + cap.
+ * d_outSizes[i] = LZ4MT_HIP_BATCH_BAD_CHUNK, and nothing written, for a
+ * chunk with a null or misaligned destination, a null source of non-zero
+ * size, or (compress) a size above maxChunkBytes.
+ *
+ * LZ4MT_RESULT_BAD_ARG: a null array with nChunks > 0 (d_dstCaps may be
+ * null for compress only), maxChunkBytes above the maximum; then
+ * LZ4MT_RESULT_ERROR without a HIP device or on a launch error; else
+ * LZ4MT_RESULT_OK (nChunks == 0 launches nothing). */
+#define LZ4MT_HIP_BATCH_MAX_CHUNK (4u << 20)
+#define LZ4MT_HIP_BATCH_BAD_CHUNK INT32_MIN
+Lz4MtResult lz4mtHipCompressBatch(const void* const* d_srcPtrs, const uint32_t* d_srcSizes, uint32_t maxChunkBytes,
+                                  uint32_t nChunks, void* const* d_dstPtrs, const uint32_t* d_dstCaps,
+                                  int32_t* d_outSizes, void* stream);
+Lz4MtResult lz4mtHipDecompressBatch(const void* const* d_srcPtrs, const uint32_t* d_srcSizes, uint32_t nChunks,
+                                    void* const* d_dstPtrs, const uint32_t* d_dstCaps, int32_t* d_outSizes,
+                                    void* stream);
+
+/* ---- 6. diagnostics ----------------------------------------------------- */
 /* Runs s_memtime-stamped twins of the encode / decode kernels (never the
  * product launch) and sums per-phase shader cycles over all blocks.
  * encode (16 slots): [hash, table+dedup, candidate check, round issue,

@@ -27,6 +27,7 @@ __all__ = [
     "compress_frame", "decompress_frame", "frame_info", "frame_bound", "gen_synthetic", "xxh32",
     "device_count", "stream_bound", "frame_records", "xxh32_chunks", "frame_header", "shard_workspace",
     "shard_pack_bound", "shard_reset", "shard_encode", "shard_pack", "shard_unpack", "shard_assemble", "shard_body_bytes",
+    "batch_compress_bound", "compress_batch", "decompress_batch", "BATCH_MAX_CHUNK", "BATCH_BAD_CHUNK",
 ]
 
 lib = _abi.load()
@@ -154,6 +155,107 @@ def _stream(stream):
 def _check_dev(t, name):
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
         raise TypeError(f"{name} must be a contiguous torch.uint8 tensor on a HIP device")
+
+
+# ---------------------------------------------------------------------------
+# batched block operators on device memory (include/lz4mt_hip.h section 5)
+# ---------------------------------------------------------------------------
+BATCH_MAX_CHUNK = _abi.BATCH_MAX_CHUNK
+BATCH_BAD_CHUNK = _abi.BATCH_BAD_CHUNK
+
+
+def batch_compress_bound(n):
+    """Capacity at which a chunk of ``n`` bytes always fits (lz4mtHipCompressBound)."""
+    return compress_bound(n)
+
+
+def _batch(fn_name, srcs, caps, null_caps, max_chunk, stream):
+    """The common part of compress_batch / decompress_batch: one backing
+    allocation for the outputs (each at a 16-byte-aligned offset, ``cap``
+    bytes long), the four descriptor arrays built on the host and uploaded
+    in one copy, one library call.  Everything is issued on ``stream``."""
+    n = len(srcs)
+    dev = srcs[0].device if n else torch.device("cuda", torch.cuda.current_device())
+    if stream is None:
+        ts = torch.cuda.current_stream(dev)
+    elif isinstance(stream, torch.cuda.Stream):
+        ts = stream
+    else:
+        ts = torch.cuda.ExternalStream(int(stream), device=dev)
+    with torch.cuda.stream(ts):
+        sizes = torch.empty(n, dtype=torch.int32, device=dev)
+        if n == 0:
+            return [], sizes
+        offs, total = [], 0
+        for c in caps:
+            offs.append(total)
+            total += (c + 15) & ~15
+        back = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+        base = back.data_ptr()
+        assert base % 16 == 0
+        # [src pointers | dst pointers] as int64, then [src sizes | capacities] as int32, in one host buffer
+        # (pinned, so that the upload is asynchronous too: the host allocator
+        # keeps the buffer until the copy has run)
+        host = torch.empty(2 * n * 8 + 2 * n * 4, dtype=torch.uint8, pin_memory=True)
+        p64 = host[:16 * n].view(torch.int64)
+        p64[:n] = torch.tensor([s.data_ptr() for s in srcs], dtype=torch.int64)
+        p64[n:] = torch.tensor([base + o for o in offs], dtype=torch.int64)
+        p32 = host[16 * n:].view(torch.int32)
+        p32[:n] = torch.tensor([s.numel() for s in srcs], dtype=torch.int64).to(torch.int32)   # (u32 bit patterns)
+        p32[n:] = torch.tensor(caps, dtype=torch.int64).to(torch.int32)
+        desc = host.to(dev, non_blocking=True)
+        d = desc.data_ptr()
+        d_src, d_dst, d_sz, d_cap = d, d + 8 * n, d + 16 * n, d + 20 * n
+        fn = getattr(lib, fn_name)
+        st = ctypes.c_void_p(ts.cuda_stream)
+        cap_arg = ctypes.c_void_p(None if null_caps else d_cap)
+        if max_chunk is None:
+            r = fn(ctypes.c_void_p(d_src), ctypes.c_void_p(d_sz), n, ctypes.c_void_p(d_dst), cap_arg,
+                   ctypes.c_void_p(sizes.data_ptr()), st)
+        else:
+            r = fn(ctypes.c_void_p(d_src), ctypes.c_void_p(d_sz), max_chunk, n, ctypes.c_void_p(d_dst), cap_arg,
+                   ctypes.c_void_p(sizes.data_ptr()), st)
+        if r != Result.OK:
+            raise Lz4MtError(r, fn_name)
+        return [back[o:o + c] for o, c in zip(offs, caps)], sizes
+
+
+def compress_batch(chunks, caps=None, stream=None):
+    """lz4mtHipCompressBatch: every tensor of ``chunks`` (contiguous uint8 on
+    one HIP device, slices at any offset included, at most 4 MiB each) as an
+    independent raw LZ4 block, in one launch.  ``caps``: a capacity per chunk
+    (default: the bound of each size).  Returns ``(outs, sizes)``: ``outs[i]``
+    a ``caps[i]``-byte view of one backing allocation, ``sizes`` the int32
+    device tensor of block sizes (0: does not fit its capacity).  Does not
+    synchronise: ``chunks`` must stay alive until ``stream`` has run the call."""
+    chunks = list(chunks)
+    for i, c in enumerate(chunks):
+        _check_dev(c, f"chunks[{i}]")
+    big = max((c.numel() for c in chunks), default=0)
+    if big > BATCH_MAX_CHUNK:
+        raise ValueError(f"a chunk of {big} bytes exceeds the batch maximum of {BATCH_MAX_CHUNK}")
+    if caps is None:
+        return _batch("lz4mtHipCompressBatch", chunks, [batch_compress_bound(c.numel()) for c in chunks], True, big,
+                      stream)
+    caps = [int(c) for c in caps]
+    if len(caps) != len(chunks) or any(c < 0 or c >= 1 << 32 for c in caps):
+        raise ValueError("caps: one capacity of 0 .. 2^32 - 1 per chunk")
+    return _batch("lz4mtHipCompressBatch", chunks, caps, False, big, stream)
+
+
+def decompress_batch(blocks, caps, stream=None):
+    """lz4mtHipDecompressBatch: every tensor of ``blocks`` (contiguous uint8
+    on one HIP device) is one raw LZ4 block, decoded into at most ``caps[i]``
+    bytes, in one launch.  Returns ``(outs, sizes)`` as
+    compress_batch does; ``sizes[i]`` is the decoded size, negative for a
+    malformed block (LZ4_decompress_safe).  Does not synchronise."""
+    blocks = list(blocks)
+    for i, b in enumerate(blocks):
+        _check_dev(b, f"blocks[{i}]")
+    caps = [int(c) for c in caps]
+    if len(caps) != len(blocks) or any(c < 0 or c >= 1 << 31 for c in caps):
+        raise ValueError("caps: one capacity of 0 .. 2^31 - 1 per block")
+    return _batch("lz4mtHipDecompressBatch", blocks, caps, False, None, stream)
 
 
 def frame_bound(n, sd=None):

@@ -19,6 +19,11 @@ constexpr int kLimit64K = 65547;
 // Decoder status codes beyond LZ4_decompress_safe's own negative values.
 constexpr int kDecodeOutputTooSmall = INT32_MIN;   // physical slot smaller than the decoded block
 
+// Batched block operators (lz4mt_hip.h section 5): the largest chunk, and the
+// per-chunk status of a chunk the kernels refuse (LZ4MT_HIP_BATCH_BAD_CHUNK).
+constexpr uint32_t kBatchMaxChunk = 4u << 20;
+constexpr int32_t kBatchBadChunk = INT32_MIN;
+
 // Per-block record of a parsed frame (device-resident, one per block).
 struct BlockRec {
     uint64_t offset;     // payload offset inside the frame
@@ -95,6 +100,14 @@ hipError_t launch_encode_pub(const uint8_t* src, uint64_t srcSize, uint32_t bloc
                              uint8_t* slots, int32_t* csize, uint32_t* pub, hipStream_t st);
 hipError_t launch_decode(const uint8_t* frame, const BlockRec* recs, uint32_t nBlocks, uint32_t blockMax,
                          uint8_t* out, uint64_t outCap, int32_t* dsize, hipStream_t st);
+// the batched block operators (k_encode_batch / k_encode_batch16 by maxChunk,
+// k_decode_batch): one wave per chunk, every array in device memory,
+// dstCaps null for the encode = the bound of each size
+hipError_t launch_encode_batch(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
+                               uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps, int32_t* outSizes,
+                               hipStream_t st);
+hipError_t launch_decode_batch(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t nChunks,
+                               uint8_t* const* dstPtrs, const uint32_t* dstCaps, int32_t* outSizes, hipStream_t st);
 // the serial frame walk fused with the decode (k_decode_walk): records are
 // decoded as the walk publishes them.  ctl: 8 zeroed device words.
 hipError_t launch_decode_walk(const uint8_t* frame, uint64_t frameSize, uint64_t bodyPos, uint32_t blockMax,

@@ -535,6 +535,35 @@ extern "C" int lz4mtHipDecompressBlock(const char* src, char* dst, int isize, in
     return r == kDecodeOutputTooSmall ? -1 : r;
 }
 
+// Batched block operators on device memory (lz4mt_hip.h section 5): one
+// launch for the batch, per-chunk outcomes in d_outSizes only.  Nothing here
+// allocates, synchronises or reads the arrays, so a call can be captured
+// into a graph (the encoder-order check then behaves as for the frame
+// engine: launch_encode_batch -> encoder_path).
+static_assert(LZ4MT_HIP_BATCH_MAX_CHUNK == kBatchMaxChunk && LZ4MT_HIP_BATCH_BAD_CHUNK == kBatchBadChunk, "batch ABI");
+extern "C" Lz4MtResult lz4mtHipCompressBatch(const void* const* d_srcPtrs, const uint32_t* d_srcSizes,
+                                             uint32_t maxChunkBytes, uint32_t nChunks, void* const* d_dstPtrs,
+                                             const uint32_t* d_dstCaps, int32_t* d_outSizes, void* stream) {
+    if (nChunks && (!d_srcPtrs || !d_srcSizes || !d_dstPtrs || !d_outSizes)) return LZ4MT_RESULT_BAD_ARG;
+    if (maxChunkBytes > LZ4MT_HIP_BATCH_MAX_CHUNK) return LZ4MT_RESULT_BAD_ARG;
+    if (!have_device()) return LZ4MT_RESULT_ERROR;
+    HIPCHK(launch_encode_batch(reinterpret_cast<const uint8_t* const*>(d_srcPtrs), d_srcSizes, maxChunkBytes, nChunks,
+                               reinterpret_cast<uint8_t* const*>(d_dstPtrs), d_dstCaps, d_outSizes,
+                               static_cast<hipStream_t>(stream)));
+    return LZ4MT_RESULT_OK;
+}
+
+extern "C" Lz4MtResult lz4mtHipDecompressBatch(const void* const* d_srcPtrs, const uint32_t* d_srcSizes,
+                                               uint32_t nChunks, void* const* d_dstPtrs, const uint32_t* d_dstCaps,
+                                               int32_t* d_outSizes, void* stream) {
+    if (nChunks && (!d_srcPtrs || !d_srcSizes || !d_dstPtrs || !d_dstCaps || !d_outSizes)) return LZ4MT_RESULT_BAD_ARG;
+    if (!have_device()) return LZ4MT_RESULT_ERROR;
+    HIPCHK(launch_decode_batch(reinterpret_cast<const uint8_t* const*>(d_srcPtrs), d_srcSizes, nChunks,
+                               reinterpret_cast<uint8_t* const*>(d_dstPtrs), d_dstCaps, d_outSizes,
+                               static_cast<hipStream_t>(stream)));
+    return LZ4MT_RESULT_OK;
+}
+
 // ===========================================================================
 // 2. device-resident frame engine
 // ===========================================================================

@@ -191,7 +191,22 @@ constexpr uint32_t kDedup = 1024;                 // duplicate-hash scratch entr
 constexpr uint32_t kOutRing = 1024;               // LDS staging of the compressed output
 constexpr uint32_t kOutFlush = 512;               // flush granule (64 lanes x 8 B)
 
-struct SrcView {
+// The first `avail` (>= 1) bytes at p, p at any alignment, in a dword: only
+// the aligned dwords that hold one of those bytes are read (ld32u when all
+// four exist).
+__device__ __forceinline__ uint32_t ld32n(g_cu8* p, uint32_t avail) {
+    const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3);
+    g_cu32* q = (g_cu32*)(p - sh);
+    const uint32_t lo = q[0];
+    const uint32_t hi = (sh && 4 - sh < avail) ? q[1] : 0u;
+    return __builtin_amdgcn_alignbyte(hi, lo, sh);
+}
+
+// UA: the block may start at any address (the batched block kernels: a
+// chunk is wherever its caller put it).  Without it s is 4-byte aligned, as
+// every block of a frame is, and a chunk is two aligned dwords.
+template <bool UA = false>
+struct SrcViewT {
     g_cu8* s;
     uint32_t n;
     l_u32* ring;      // kRingE bytes
@@ -202,8 +217,13 @@ struct SrcView {
     __device__ __forceinline__ void fetch(uint32_t c, uint32_t& a, uint32_t& b) const {
         const uint32_t pos = c + 8 * laneid();
         a = 0; b = 0;
-        if (pos < n) a = *(g_cu32*)(s + pos);
-        if (pos + 4 < n) b = *(g_cu32*)(s + pos + 4);
+        if constexpr (UA) {
+            if (pos < n) a = ld32n(s + pos, n - pos);
+            if (pos + 4 < n) b = ld32n(s + pos + 4, n - pos - 4);
+        } else {
+            if (pos < n) a = *(g_cu32*)(s + pos);
+            if (pos + 4 < n) b = *(g_cu32*)(s + pos + 4);
+        }
     }
     __device__ __forceinline__ void store(uint32_t c, uint32_t a, uint32_t b) {
         const uint32_t w = (c >> 2) + 2 * laneid();
@@ -258,6 +278,7 @@ struct SrcView {
         return s[pos];
     }
 };
+using SrcView = SrcViewT<false>;
 
 // Compressed output staged in a 1 KiB LDS ring; complete 512-byte chunks are
 // flushed with 8-byte stores.  Global stores are rare, so the vmcnt waits of
@@ -292,7 +313,8 @@ __device__ __forceinline__ uint32_t ext_len(uint32_t v) { return (v + 240) / 255
 // Stages literal bytes src[from + i] for i in [i0, i1) at out position
 // base + i, 4 per lane, flushing complete chunks below `safe + i` between
 // pieces (bytes below `safe` are final).
-__device__ __forceinline__ void stage_lits(const SrcView& V, OutView& O, uint32_t from, uint32_t i0, uint32_t i1,
+template <bool UA>
+__device__ __forceinline__ void stage_lits(const SrcViewT<UA>& V, OutView& O, uint32_t from, uint32_t i0, uint32_t i1,
                                            uint32_t base, bool flush, uint32_t safe) {
     const uint32_t L = laneid();
     for (uint32_t piece = i0; piece < i1; piece += 256) {
@@ -355,7 +377,7 @@ struct LinkArgs {
     uint32_t shift = 0;
 };
 
-template <bool U16, bool TAG, bool ST, bool LINK = false>
+template <bool U16, bool TAG, bool ST, bool LINK = false, bool UA = false>
 __device__ __forceinline__ int32_t encode_block(g_cu8* __restrict__ s, uint32_t n, g_u8* __restrict__ d, uint32_t cap,
                                 l_u32* __restrict__ Traw, l_u8* __restrict__ S, l_u32* __restrict__ ringE,
                                 l_u8* __restrict__ outRing, uint64_t* acc, LinkArgs lk = LinkArgs{0, 0, 0, true}) {
@@ -378,7 +400,7 @@ __device__ __forceinline__ int32_t encode_block(g_cu8* __restrict__ s, uint32_t 
         l_u4* T4 = (l_u4*)Traw;
         for (uint32_t i = L; i < 1024; i += 64) T4[i] = (v4u){t0, t0, t0, t0};
     }
-    SrcView V{s, n, ringE, 0, 0, 0, 0};
+    SrcViewT<UA> V{s, n, ringE, 0, 0, 0, 0};
     V.init(o0);
     OutView O{d, outRing, 0};
 
@@ -1496,6 +1518,86 @@ __global__ void __launch_bounds__(64) k_encode16(const uint8_t* __restrict__ src
     if (laneid() == 0) csize[b] = r;
 }
 
+// ---- batched block operators (lz4mt_hip.h section 5): wave blockIdx.x
+// compresses chunk blockIdx.x, an independent raw block.  Source, size,
+// destination and capacity come from device arrays, read at a uniform index
+// (scalar loads); nothing is derived from a block size or a slot stride.
+// What a frame's slots grant and a caller's buffers do not:
+//   * a source at any address, ending on its allocation's last byte: the
+//     v5 parser reads the source with unaligned loads clamped to [0, n)
+//     and by bytes, encode_block takes its ring chunks through ld32n (UA);
+//   * exact capacities: both parsers store only bytes below the output
+//     cursor, which 1.9.3's limitedOutput margins keep at or below cap
+//     (encode_block's 8-byte flushes, of whole 512-byte granules below the
+//     cursor, need the destination's alignment, checked here per chunk).
+// No wait on another wave, no loop over chunks, no atomics: a wave that
+// runs ends.
+// One chunk's descriptor; bad: LZ4MT_HIP_BATCH_BAD_CHUNK, nothing written.
+struct BatchChunk {
+    g_cu8* s;
+    g_u8* d;
+    uint32_t n, cap;
+    bool bad;
+};
+__device__ __forceinline__ BatchChunk batch_chunk(const uint8_t* const* __restrict__ srcPtrs,
+                                                  const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
+                                                  uint8_t* const* __restrict__ dstPtrs,
+                                                  const uint32_t* __restrict__ dstCaps) {
+    const uint32_t i = blockIdx.x;
+    BatchChunk c;
+    c.n = srcSizes[i];
+    const uint8_t* sp = srcPtrs[i];
+    uint8_t* dp = dstPtrs[i];
+    c.s = gptr(sp);
+    c.d = gptr(dp);
+    c.cap = dstCaps ? dstCaps[i] : c.n + c.n / 255 + 16;   // lz4mtHipCompressBound
+    c.bad = c.n > maxChunk || !dp || (reinterpret_cast<uintptr_t>(dp) & 15) != 0 || (!sp && c.n != 0);
+    return c;
+}
+
+// Chunks of any size up to 4 MiB (maxChunk <= 1 << kPosBits, checked by the
+// host): k_encode's LDS layout and per-block choice, 20 KiB and 8 waves per
+// CU.  The byU32 parser is k_encode's instantiation, inlined here as there.
+template <bool XC>
+__global__ void __launch_bounds__(64) k_encode_batch(const uint8_t* const* __restrict__ srcPtrs,
+                                                     const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
+                                                     uint8_t* const* __restrict__ dstPtrs,
+                                                     const uint32_t* __restrict__ dstCaps,
+                                                     int32_t* __restrict__ outSizes) {
+    ENCODE_LDS
+    const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, dstCaps);
+    l_u8* Xl = (l_u8*)X;
+    int32_t r;
+    if (c.bad)
+        r = kBatchBadChunk;
+    else if (c.n < (uint32_t)kLimit64K)
+        r = encode_block<true, false, false, false, true>(c.s, c.n, c.d, c.cap, (l_u32*)T, (l_u8*)S, (l_u32*)Xl,
+                                                          Xl + kRingE, nullptr);
+    else
+        [[clang::always_inline]] r =
+            encode_block_v5<false, false, false, false, false, false, false, XC>(c.s, c.n, c.d, c.cap, (l_u32*)T, Xl,
+                                                                                 nullptr);
+    if (laneid() == 0) outSizes[blockIdx.x] = r;
+}
+
+// Every chunk below 65 547 bytes (maxChunk < kLimit64K): k_encode16's split
+// byU16 table, 26.3 KiB and 6 waves per CU.  An instantiation of its own
+// (DUP), so that k_encode16's stays the single call site it is inlined at.
+template <bool XC>
+__global__ void __launch_bounds__(64) k_encode_batch16(const uint8_t* const* __restrict__ srcPtrs,
+                                                       const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
+                                                       uint8_t* const* __restrict__ dstPtrs,
+                                                       const uint32_t* __restrict__ dstCaps,
+                                                       int32_t* __restrict__ outSizes) {
+    __shared__ uint32_t E16[kE16Words];
+    const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, dstCaps);
+    int32_t r = kBatchBadChunk;
+    if (!c.bad)
+        [[clang::always_inline]] r = encode_block_v5<false, true, true, false, false, false, false, XC, true>(
+            c.s, c.n, c.d, c.cap, (l_u32*)E16, (l_u8*)(E16 + kE16TabWords), nullptr);
+    if (laneid() == 0) outSizes[blockIdx.x] = r;
+}
+
 // A block-dependent table entry (position | tag, V5Geo<false, false, true>)
 // in the next block's coordinates: position x -> x - n; positions at or
 // below n (older than the next block's 64 KiB window) -> 0, stale like an
@@ -1951,6 +2053,28 @@ hipError_t launch_encode(const uint8_t* src, uint64_t srcSize, uint32_t blockSiz
                            capOverride, csize);
     return hipGetLastError();
 }
+
+// All arrays are device memory; dstCaps may be null (every capacity the
+// bound).  maxChunk <= kBatchMaxChunk (the caller checked).  A grid holds at
+// most kBatchGrid chunks; longer batches go out in slices of the arrays.
+constexpr uint32_t kBatchGrid = 1u << 30;
+hipError_t launch_encode_batch(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
+                               uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps, int32_t* outSizes,
+                               hipStream_t st) {
+    bool xc = true;
+    if (const hipError_t r = encoder_path(st, &xc); r != hipSuccess) return r;
+    const bool small = maxChunk < (uint32_t)kLimit64K;
+    const auto k = small ? (xc ? k_encode_batch16<true> : k_encode_batch16<false>)
+                         : (xc ? k_encode_batch<true> : k_encode_batch<false>);
+    for (uint32_t o = 0; o < nChunks;) {
+        const uint32_t g = std::min(nChunks - o, kBatchGrid);
+        hipLaunchKernelGGL(k, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, maxChunk, dstPtrs + o,
+                           dstCaps ? dstCaps + o : nullptr, outSizes + o);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        o += g;
+    }
+    return hipSuccess;
+}
 #endif
 
 
@@ -2012,7 +2136,10 @@ constexpr int32_t kFpOff = kInWin + 128 + 1040;
 [[maybe_unused]] constexpr int32_t kWinAlloc = kFpOff + 16 * kFarTab;
 static_assert(kRing + kWinAlloc <= 20480 || kRing != 16384, "decoder LDS: 8 waves per CU need <= 20 KiB each");
 
-template <bool ST>
+// HG: no dword that lies wholly before src is read either (the batched
+// block kernel: nothing of the caller's precedes a chunk).  A frame's block
+// has the frame before it, so the window's first 16 bytes load whole.
+template <bool ST, bool HG = false>
 struct Dec {
     uint64_t* acc;
     uint64_t ts;
@@ -2039,7 +2166,16 @@ struct Dec {
             const uintptr_t a = base + (uintptr_t)(h * 1024 + 16 * L);
             g_cu32* q = (g_cu32*)(src + (a - reinterpret_cast<uintptr_t>(src)));
             v4u v = {0, 0, 0, 0};   // dword-granular: never past the block's last dword
-            if (a + 12 < end) v = *(g_cu4*)q;
+            if constexpr (HG) {
+                const uintptr_t beg = reinterpret_cast<uintptr_t>(src);
+                if (a + 12 < end && a + 4 > beg) v = *(g_cu4*)q;
+                else {
+                    if (a < end && a + 4 > beg) v.x = q[0];
+                    if (a + 4 < end && a + 8 > beg) v.y = q[1];
+                    if (a + 8 < end && a + 12 > beg) v.z = q[2];
+                    if (a + 12 < end) v.w = q[3];
+                }
+            } else if (a + 12 < end) v = *(g_cu4*)q;
             else {
                 if (a < end) v.x = q[0];
                 if (a + 4 < end) v.y = q[1];
@@ -2489,8 +2625,8 @@ struct Dec {
 
 // LZ4_decompress_safe (lz4 1.9.3, LZ4_FAST_DEC_LOOP=1): same accept/reject
 // decisions and return values as the oracle restatement (oracle/lz4_oracle.c).
-template <bool ST>
-__device__ int32_t decode_block(Dec<ST>& D, int64_t cap) {
+template <bool ST, bool HG>
+__device__ int32_t decode_block(Dec<ST, HG>& D, int64_t cap) {
     const int64_t iend = D.len, oend = cap;
     const int64_t shortiend = iend - 16, shortoend = oend - 32;
     int64_t ip = 0, op = 0, cpy = 0, match = 0, length = 0, ext = 0;
@@ -2712,6 +2848,50 @@ __global__ void __launch_bounds__(64) k_decode(const uint8_t* __restrict__ frame
     const uint32_t b = blockIdx.x;
     const int32_t res = decode_one(frame, recs[b], b, blockMax, out, outCap, (l_u8*)ring, (l_u8*)win);
     if (laneid() == 0) dsize[b] = res;
+}
+
+// Batched block operator (lz4mt_hip.h section 5): wave blockIdx.x decodes
+// chunk blockIdx.x, always an LZ4 block (no frame bit, so never raw), into a
+// destination of exactly dstCaps[i] bytes: the slot that exists is the
+// capacity (physcap = cap), so every store is bounded by it.  The input
+// window loads no dword outside the chunk (Dec's HG).  k_decode's LDS, 8
+// waves per CU; as k_encode_batch, nothing here waits on another wave.
+__global__ void __launch_bounds__(64) k_decode_batch(const uint8_t* const* __restrict__ srcPtrs,
+                                                     const uint32_t* __restrict__ srcSizes,
+                                                     uint8_t* const* __restrict__ dstPtrs,
+                                                     const uint32_t* __restrict__ dstCaps,
+                                                     int32_t* __restrict__ outSizes) {
+    __shared__ __attribute__((aligned(16))) uint8_t ring[kRing];
+    __shared__ __attribute__((aligned(16))) uint8_t win[kWinAlloc];
+    const uint32_t i = blockIdx.x;
+    const uint32_t len = srcSizes[i], cap = dstCaps[i];
+    const uint8_t* sp = srcPtrs[i];
+    uint8_t* dp = dstPtrs[i];
+    int32_t res;
+    if (!dp || (reinterpret_cast<uintptr_t>(dp) & 15) != 0 || (!sp && len != 0)) {
+        res = kBatchBadChunk;
+    } else if (len > 0x7FFFFFFFu || cap > 0x7FFFFFFFu) {
+        res = -1;   // lz4mtHipDecompressBlock's answer to a size or capacity that is no int
+    } else {
+        Dec<false, true> D;
+        D.acc = nullptr;
+        D.ts = 0;
+        D.src = gptr(sp);
+        D.len = (int64_t)len;
+        D.dst = gptr(dp);
+        D.physcap = (int64_t)cap;
+        D.ring = (l_u8*)ring;
+        D.win = (l_u8*)win;
+        D.wlo = INT64_MIN / 4;
+        D.labase = INT64_MIN / 4;
+        D.la = 0;
+        D.flushed = 0;
+        D.completed = 0;
+        D.lowP = 0;
+        res = decode_block(D, (int64_t)cap);
+        if (res == kDecodeOutputTooSmall) res = -1;   // (unreachable with physcap = cap; mapped as the block operator maps it)
+    }
+    if (laneid() == 0) outSizes[i] = res;
 }
 
 // The serial frame walk fused with the decode (wherever the walk is serial,
@@ -3296,6 +3476,19 @@ hipError_t launch_decode(const uint8_t* frame, const BlockRec* recs, uint32_t nB
     if (nBlocks == 0) return hipSuccess;
     hipLaunchKernelGGL(k_decode, dim3(nBlocks), dim3(64), 0, st, frame, recs, blockMax, out, outCap, dsize);
     return hipGetLastError();
+}
+
+hipError_t launch_decode_batch(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t nChunks,
+                               uint8_t* const* dstPtrs, const uint32_t* dstCaps, int32_t* outSizes, hipStream_t st) {
+    constexpr uint32_t kGrid = 1u << 30;   // chunks per grid; longer batches go out in slices of the arrays
+    for (uint32_t o = 0; o < nChunks;) {
+        const uint32_t g = std::min(nChunks - o, kGrid);
+        hipLaunchKernelGGL(k_decode_batch, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, dstPtrs + o,
+                           dstCaps + o, outSizes + o);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        o += g;
+    }
+    return hipSuccess;
 }
 #endif
 

@@ -1,0 +1,154 @@
+"""Batched block operators (lz4mtHipCompressBatch / lz4mtHipDecompressBatch)
+on App. F synthetic input cut into uniform chunks of 4 KiB, 64 KiB and 1 MiB
+and one ragged mix of 1 KiB .. 256 KiB, timed with device events (2 warm-up
+calls discarded, median of 10), beside the frame engine's encode and decode
+kernels on the same bytes at -B4 and -B6 (-Sx, no block checksum) as the
+yardstick: the 64 KiB and 1 MiB batch kernels run the same window code on
+the same blocks.  Prints one JSON line.
+
+    python tools/batch_bench.py [--gib 1] [--reps 10]
+
+Capacities are the default (d_dstCaps = NULL: the bound of each size), the
+frame encoder's are the block size; every configuration is decoded back and
+compared with the input once, outside the timed calls.
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import lz4mt_amd as L  # noqa: E402
+
+P = ctypes.c_void_p
+
+
+def timed(fn, reps, warm=2):
+    """median, min, max (ms, device events) of `reps` calls after `warm` discarded ones"""
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return statistics.median(ms), min(ms), max(ms)
+
+
+def batch_row(name, src, sizes, reps):
+    n = len(sizes)
+    total = int(sizes.sum())
+    soff = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+    caps = sizes + sizes // 255 + 16
+    stride = (caps + 15) & ~np.int64(15)
+    doff = np.concatenate([[0], np.cumsum(stride)[:-1]]).astype(np.int64)
+    comp = torch.empty(int(stride.sum()), dtype=torch.uint8, device="cuda")
+    back = torch.empty(int(((sizes + 15) & ~np.int64(15)).sum()), dtype=torch.uint8, device="cuda")
+    boff = np.concatenate([[0], np.cumsum((sizes + 15) & ~np.int64(15))[:-1]]).astype(np.int64)
+    sp = torch.from_numpy(soff + src.data_ptr()).cuda()
+    cp = torch.from_numpy(doff + comp.data_ptr()).cuda()
+    bp = torch.from_numpy(boff + back.data_ptr()).cuda()
+    sz = torch.from_numpy(sizes.astype(np.uint32).view(np.int32)).cuda()
+    csz = torch.zeros(n, dtype=torch.int32, device="cuda")
+    dsz = torch.zeros(n, dtype=torch.int32, device="cuda")
+    max_chunk = int(sizes.max())
+    st = P(torch.cuda.current_stream().cuda_stream)
+
+    def enc():
+        r = L.lib.lz4mtHipCompressBatch(P(sp.data_ptr()), P(sz.data_ptr()), max_chunk, n, P(cp.data_ptr()), None,
+                                        P(csz.data_ptr()), st)
+        assert r == 0, r
+
+    def dec():
+        r = L.lib.lz4mtHipDecompressBatch(P(cp.data_ptr()), P(csz.data_ptr()), n, P(bp.data_ptr()), P(sz.data_ptr()),
+                                          P(dsz.data_ptr()), st)
+        assert r == 0, r
+
+    e = timed(enc, reps)
+    d = timed(dec, reps)
+    # round trip, once: sizes and bytes
+    assert bool((csz > 0).all()) and torch.equal(dsz, sz), name
+    if bool(np.all(boff[1:] - boff[:-1] == sizes[:-1])):   # outputs contiguous: one compare
+        assert torch.equal(back[:total], src[:total]), name
+    else:
+        for i in np.random.RandomState(1).choice(n, size=min(n, 2000), replace=False):
+            a, b, k = int(boff[i]), int(soff[i]), int(sizes[i])
+            assert torch.equal(back[a:a + k], src[b:b + k]), (name, int(i))
+    cbytes = int(csz.sum().item())
+    gib = total / 2**30
+    return {"name": name, "chunks": n, "bytes": total, "max_chunk": max_chunk,
+            "kernel": "k_encode_batch16" if max_chunk < 65547 else "k_encode_batch", "ratio": round(total / cbytes, 4),
+            "compress_ms": round(e[0], 3), "compress_ms_min_max": [round(e[1], 3), round(e[2], 3)],
+            "compress_gib_s": round(gib / (e[0] / 1e3), 2),
+            "decompress_ms": round(d[0], 3), "decompress_ms_min_max": [round(d[1], 3), round(d[2], 3)],
+            "decompress_gib_s": round(gib / (d[0] / 1e3), 2)}
+
+
+def frame_row(src, bid, reps):
+    """the frame engine's encode kernel (timing slot 0 of the compress call) and
+    decode kernel (slot 1 of the decompress call), as tools/ktime.py reads them"""
+    sd = L.make_sd(bid, False, False)
+    ws = L.compress_workspace(src.numel(), sd)
+    out = torch.empty(L.frame_bound(src.numel(), sd), dtype=torch.uint8, device="cuda")
+    dst = torch.empty(src.numel() + (4 << 20), dtype=torch.uint8, device="cuda")
+    ms = (ctypes.c_float * 4)()
+    L.lib.lz4mtHipSetTiming(1)
+    enc, dec = [], []
+    for i in range(reps + 2):
+        fr = L.compress_frame(src, sd, out=out, workspace=ws)
+        assert L.lib.lz4mtHipGetTimings(ms) == 0
+        e = ms[0]
+        got, r = L.decompress_frame(fr, out=dst)
+        assert r == 0 and L.lib.lz4mtHipGetTimings(ms) == 0
+        if i >= 2:
+            enc.append(e)
+            dec.append(ms[1])
+    L.lib.lz4mtHipSetTiming(0)
+    assert torch.equal(got, src)
+    gib = src.numel() / 2**30
+    e, d = statistics.median(enc), statistics.median(dec)
+    return {"name": f"frame -B{bid} -Sx", "block": 1 << (8 + 2 * bid), "encode_kernel_ms": round(e, 3),
+            "encode_kernel_ms_min_max": [round(min(enc), 3), round(max(enc), 3)],
+            "encode_gib_s": round(gib / (e / 1e3), 2), "decode_kernel_ms": round(d, 3),
+            "decode_kernel_ms_min_max": [round(min(dec), 3), round(max(dec), 3)],
+            "decode_gib_s": round(gib / (d / 1e3), 2)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gib", type=float, default=1.0)
+    ap.add_argument("--reps", type=int, default=10)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("batch_bench.py needs a HIP device")
+    n = int(a.gib * 2**30) & ~((1 << 20) - 1)
+    src = L.gen_synthetic(n, seed=42)
+    rows = []
+    for name, k in (("4KiB", 4 << 10), ("64KiB", 64 << 10), ("1MiB", 1 << 20)):
+        rows.append(batch_row(name, src, np.full(n // k, k, dtype=np.int64), a.reps))
+    rs = np.random.RandomState(7)
+    sizes = rs.randint(1 << 10, (256 << 10) + 1, size=2 * n // (128 << 10) + 16).astype(np.int64)
+    sizes = sizes[:int(np.searchsorted(np.cumsum(sizes), n, side="right"))]
+    rows.append(batch_row("ragged 1KiB-256KiB", src, sizes, a.reps))
+    frames = [frame_row(src, 4, a.reps), frame_row(src, 6, a.reps)]
+    by = {r["name"]: r for r in rows}
+    gaps = {}
+    for nm, fr in (("64KiB", frames[0]), ("1MiB", frames[1])):
+        gaps[nm] = {"encode_vs_frame_kernel": round(by[nm]["compress_ms"] / fr["encode_kernel_ms"], 4),
+                    "decode_vs_frame_kernel": round(by[nm]["decompress_ms"] / fr["decode_kernel_ms"], 4)}
+    print(json.dumps({"tool": "batch_bench", "device": torch.cuda.get_device_name(0), "input": "gen_synthetic seed 42",
+                      "bytes": n, "reps": a.reps, "warmup": 2, "stat": "median", "batch": rows, "frame": frames,
+                      "batch_over_frame_kernel": gaps}))
+
+
+if __name__ == "__main__":
+    main()
