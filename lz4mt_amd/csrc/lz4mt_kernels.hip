@@ -858,10 +858,21 @@ __device__ __forceinline__ uint32_t pend_byte(const SeqLayout<R8>& e, uint32_t x
 // stays selects (no load sunk into a branch) and the store waits only on the
 // counter of its own load: LDS (ring, the common case) never waits on the
 // round-trip loads in flight.
-template <bool R8>
+// FS (the fast body of encode_block_v5, LZ4MT_FAST_WINDOW bit 32):
+//   kPendRingLo   the caller has advanced the ring past the literals' end
+//                 (V.cover(hi), hi above the window's sBase and the literals
+//                 below it), so "in the ring" is the lower bound alone;
+//   kPendNoBytes  timing builds only (LZ4MT_EXP_NO_PEND_BYTES): no byte
+//                 rounds at all, the output is wrong.
+constexpr int kPendRingLo = 1, kPendNoBytes = 4;
+template <bool R8, int FS = 0>
 __device__ __forceinline__ void store_pend(const PendSeq& p, const SrcRing& V, g_cu8* __restrict__ s,
                                            g_u8* __restrict__ d) {
+    if constexpr ((FS & kPendNoBytes) != 0) return;
     const uint32_t L = laneid();
+    // (inRing: evaluated where it is used, V.B is not re-read in between)
+#define LZ4MT_PEND_IN_RING \
+    ((FS & kPendRingLo) ? p.anchor >= V.B : p.anchor >= V.B && p.anchor + p.lit <= V.B + kSR)
     // the layout in VALU (uniform values in VGPRs): the scalar unit is the
     // CU's busiest port in the encoder window, the vector ALU is not
     PendSeq q = p;
@@ -870,7 +881,8 @@ __device__ __forceinline__ void store_pend(const PendSeq& p, const SrcRing& V, g
     const uint32_t total = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.total);
     // a sequence is at least 5 bytes: the first round always runs (no
     // zero-trip test before the loop)
-    if (p.anchor >= V.B && p.anchor + p.lit <= V.B + kSR) {
+    if (LZ4MT_PEND_IN_RING) {
+#undef LZ4MT_PEND_IN_RING
         uint32_t base = 0;
         do {
             const uint32_t x = min(base + L, e.total - 1);   // lanes past the end repeat the last byte
@@ -1161,6 +1173,22 @@ __device__ int32_t encode_block_v5(g_cu8* __restrict__ s, uint32_t n, g_u8* __re
     //   does not cover: after a match by ipe >= fastEndS (in place of the
     //   general ipe >= mflimitP1), after a continuation by the new sBase and
     //   spanHi.  It is entered after a match only (spanHi = 61).
+    //   (c) begin distance (bit 16).  The phase is entered only after a match
+    //       with ipe >= fastBegS = o0 + 65536 + 64, and ipe never falls, so
+    //       every stop of the phase has ip >= ipe >= 65536 + 64 and its
+    //       candidate, at most 65535 below, cd >= 65 > 64: the 16 backward
+    //       words at cd - 4 .. cd - 64 (and those below ip) lie inside the
+    //       block -- also in block 0 of a buffer and in a chunk of
+    //       k_encode_batch that starts on its allocation's first byte.  A
+    //       fast window is the first after a match: anchor = sBase - 1, lane
+    //       w probes sBase + w - 2 (the TEST lane, w = 1, sBase - 1), so
+    //       ip - anchor = w - 1 <= 62 < cd and lz4's catch-up bound
+    //       min(ip - anchor, cd - 0) is w - 1: 64 bytes below the stop
+    //       always reach it, the loops for longer catch-ups cannot run.
+    //   (d) ring bound (bit 32).  A fast window is never wide, so its
+    //       V.cover(hi) has run and hi <= V.B + kSR; the pending literals end
+    //       at or below the previous stop, below sBase < hi: the store's
+    //       in-ring test is anchor >= V.B alone.
     // LZ4MT_FAST_WINDOW (A/B builds): 0 the one general loop (also
     // -DLZ4MT_NO_FAST_WINDOW); 1 the fast phase without the end predicates
     // and clamps; + 2 without the margin test, entered once (b) holds;
@@ -1170,19 +1198,56 @@ __device__ int32_t encode_block_v5(g_cu8* __restrict__ s, uint32_t n, g_u8* __re
     // without a stop leaves the phase: the general body resumes the search
     // from the continuation state (k0 = 62) and the phase is entered again
     // after its match.  Without bit 8 the loop is the one of bits 1 + 2 + 4.
+    // + 16 (needs 8): the catch-up bytes come as 16 words below cd / ip in
+    // the round trip's idle count lanes, the bound is w - 1, no catch-up
+    // loops, and the phase begins at fastBegS, (c); + 32 (needs 4 and 8): the
+    // pending store's in-ring test is its lower bound alone, (d).  Without
+    // bits 16 and 32 the encoder object is the one of 15.
 #ifndef LZ4MT_FAST_WINDOW
 #ifdef LZ4MT_NO_FAST_WINDOW
 #define LZ4MT_FAST_WINDOW 0
 #else
-#define LZ4MT_FAST_WINDOW 15
+#define LZ4MT_FAST_WINDOW 63
 #endif
 #endif
     constexpr bool kFastT = (LZ4MT_FAST_WINDOW & 1) && !ST && !U16 && !SPLIT && !LINK && !P17 && !PUB && !XH && !DUP;
     constexpr bool kFastMargin = (LZ4MT_FAST_WINDOW & 2) != 0, kFastNoWide = (LZ4MT_FAST_WINDOW & 4) != 0;
     constexpr bool kFastFirst = (LZ4MT_FAST_WINDOW & 8) != 0;
+    constexpr bool kFastCatchW = kFastFirst && (LZ4MT_FAST_WINDOW & 16) != 0;
+    // (the ring bound needs the window's V.cover(hi) to have run: no wide windows)
+    [[maybe_unused]] constexpr bool kFastRingLo = kFastFirst && kFastNoWide && (LZ4MT_FAST_WINDOW & 32) != 0;
+#ifdef LZ4MT_EXP_NO_PEND_BYTES   // timing builds only: the fast body's pending store writes no bytes
+    constexpr int kFastStoreFS = kPendNoBytes;
+#else
+    constexpr int kFastStoreFS = kFastRingLo ? kPendRingLo : 0;
+#endif
+    // the fast body's pending store is store_pend<kPendR8, kFastStoreFS>
+#ifndef LZ4MT_EXP_R8ALL
+    [[maybe_unused]] constexpr bool kPendR8 = U16 || P17;
+#else
+    [[maybe_unused]] constexpr bool kPendR8 = LZ4MT_EXP_R8ALL != 0;
+#endif
     // first window after a match: lane L's position minus sBase (INSERT
     // sBase - 3, TEST sBase - 1, SEARCH sBase + L - 2)
     const uint32_t firstOff = L == 0 ? (uint32_t)-3 : (L == 1 ? (uint32_t)-1 : L - 2);
+    // kFastCatchW, the round trip's word of lane L, as an offset from cd and
+    // from ip: lane 0 the verify word, lanes 1 .. kCountLanes the forward
+    // count words, the kCatchWords lanes behind them the words BELOW cd / ip
+    // (lane kCountLanes + 1 + i: bytes -4(i+1) .. -4i-1), the rest lane 0's
+    constexpr uint32_t kCatchWords = 16;
+#ifndef LZ4MT_CATCH_GATE
+#define LZ4MT_CATCH_GATE 1
+#endif
+    [[maybe_unused]] constexpr bool kCatchGate = LZ4MT_CATCH_GATE != 0;
+    static_assert(kCountLanes + 1 + kCatchWords <= 64, "catch-up word lanes");
+    [[maybe_unused]] constexpr uint64_t kBackLanes = ((1ull << kCatchWords) - 1ull) << (kCountLanes + 1);
+    uint32_t rtOff = 0;
+    if constexpr (kFastCatchW && kFastT)
+        rtOff = L <= kCountLanes ? 4 * L : (L <= kCountLanes + kCatchWords ? 4 * kCountLanes - 4 * L : 0u);
+    // ipe >= fastBegS: every stop of the phase has ip >= 65536 + 64, so its
+    // candidate cd >= ip - 65535 lies 64 bytes or more into the block
+    constexpr uint32_t kFastBeg = kDistMax + 1 + 4 * kCatchWords;
+    [[maybe_unused]] const uint32_t fastBegS = o0 + kFastBeg;
     constexpr uint32_t kFastSpanMax = 1016;   // hi - lo = spanHi + 8 <= 1024
     // sBase + kFastSpanMax + 17 (step) + 4 + 4 kCountLanes + 8 < n - kMfLimit, with room to spare
     constexpr uint32_t kFastEndGap = 1280;

@@ -11,6 +11,10 @@
 {
     constexpr bool FAST = V5_FAST;
     constexpr bool FIRST = FAST && kFastFirst;
+    // CW (LZ4MT_FAST_WINDOW bit 16): the catch-up bytes come as words in the
+    // round trip's idle count lanes; STF (bit 32): the leaner pending store
+    constexpr bool CW = FAST && kFastCatchW;
+    constexpr bool STF = FIRST && kFastStoreFS != 0;
     bool sw = false;   // leave this phase
     bool fcont = false;   // FIRST: the phase was left by a window without a stop
     // ONE exit and no continue: the structurizer then needs no flow
@@ -192,10 +196,30 @@
                 if (w < 64 && !wTerm) {
                     ip = rdlane(p, (int)w);
                     cd = rdlane(cand, (int)w);
-                    {   // catch-up bound: lz4's lowLimit for the candidate's side
+                    if constexpr (CW) {
+                        // first window after a match: anchor = sBase - 1 and lane w
+                        // probes sBase + w - 2 (the TEST lane sBase - 1), so
+                        // ip - anchor = w - 1, and cd >= 64 > w - 1 (fastBegS)
+                        maxb = w - 1;
+                    } else {   // catch-up bound: lz4's lowLimit for the candidate's side
                         const uint32_t lowL = !LINK ? 0u : (cd >= o0 ? lk.lowIn : lk.lowDict);
                         maxb = w == 1 ? 0u : min(ip - anchor, cd > lowL ? cd - lowL : 0u);
                     }
+                    if constexpr (CW) {
+                        // lane 0: verify word; lanes 1 .. kCountLanes: count words;
+                        // the next kCatchWords lanes: the 64 bytes below cd / ip as
+                        // words (cd >= 64: inside the block); the rest repeat lane
+                        // 0's address: one add of the lane's constant offset.  A
+                        // backward lane whose word lies wholly beyond the bound
+                        // (4 i >= maxb) also repeats lane 0's address, so fewer
+                        // candidate-side lines are touched; whatever it then
+                        // reports, 4 i + e >= maxb and the bound decides
+                        // (LZ4MT_CATCH_GATE=0, A/B builds: every backward lane loads)
+                        const uint32_t ro =
+                            !kCatchGate || (int32_t)rtOff >= -(int32_t)((maxb + 3) & ~3u) ? rtOff : 0u;
+                        cw = xld4(cd + ro);
+                        iw = gld4u(s + (ip + ro));
+                    } else {
                     // lane 0: verify word; lanes 1 .. kCountLanes: count words; the
                     // rest repeat lane 0's address (no further lines touched)
                     const bool cOn = L <= kCountLanes;
@@ -211,7 +235,15 @@
                     asm volatile("" : "+v"(bix), "+v"(bcx));   // 32-bit offsets, SGPR-base loads
                     bi = s[bix];
                     bc = xld1(bcx);
-                    if (havePe) store_pending();
+                    }
+                    if (havePe) {
+                        if constexpr (STF) {
+                            store_pend<kPendR8, kFastStoreFS>(pe, V, s, d);
+                            havePe = false;
+                        } else {
+                            store_pending();
+                        }
+                    }
                     table_writes(w, false, ip);   // in the round trip's shadow; redone if w moves
                     twDone = true;
                     if (((mm >> w) & 1) && rdlane(cw, 0) != rdlane(w0, (int)w)) {   // tag alias: no match here
@@ -228,7 +260,14 @@
                 }
             }
         }
-        if (havePe) store_pending();
+        if (havePe) {
+            if constexpr (STF) {
+                store_pend<kPendR8, kFastStoreFS>(pe, V, s, d);
+                havePe = false;
+            } else {
+                store_pending();
+            }
+        }
         // no stop in the window (w == 64): every insert stays, nothing to put
         // back -- unless an alias moved the stop here after the lanes past the
         // old one were put back (twRedo: they insert again)
@@ -263,9 +302,11 @@
             // ---- catch-up (backwards) and LZ4_count (forwards from ip + 4).
             // bi/bc are consumed on every path, so no load of this window is
             // left pending into the next window's round trip.
-            asm volatile("" ::"v"(bi), "v"(bc));
-            uint64_t fm = ~(bal(L < maxb) & bal(bi == bc)) & kCatchMask;
+            uint64_t fm = 0;
             uint32_t back = 0;
+            if constexpr (!CW) {
+            asm volatile("" ::"v"(bi), "v"(bc));
+            fm = ~(bal(L < maxb) & bal(bi == bc)) & kCatchMask;
             if (kCatchLanes < 64 && fm == 0) {   // every loaded byte matched, the limit lies beyond them
                 back = kCatchLanes;
                 const uint32_t kb = back + L + 1;
@@ -279,17 +320,38 @@
                 fm = ~bal(on && s[on ? ip - kb : o0] == xld1(on ? cd - kb : o0));
             }
             back = fm ? back + (uint32_t)__builtin_ctzll(fm) : maxb;
+            }
             const uint32_t lim = matchlimit - (ip + kMinMatch);
             uint32_t mc;
             {
                 const uint32_t rel = 4 * L - 4;
                 const uint32_t x = cw ^ iw;
-                uint32_t e = x ? ((uint32_t)__builtin_ctz(x) >> 3) : 4u;
+                uint32_t e;
+                if constexpr (CW) {
+                    // equal bytes from the word's near end: its low end in a
+                    // forward lane, its high end in a backward one
+                    const bool bk = __builtin_amdgcn_inverse_ballot_w64(kBackLanes);
+                    e = x ? ((bk ? (uint32_t)__builtin_clz(x) : (uint32_t)__builtin_ctz(x)) >> 3) : 4u;
+                } else {
+                    e = x ? ((uint32_t)__builtin_ctz(x) >> 3) : 4u;
+                }
                 if constexpr (!FAST) {   // (fast phase: lim >= 4 kCountLanes)
                     e = min(e, lim - rel);
                     e = rel < lim ? e : 0u;   // (lane 0's e is masked out below)
                 }
-                const uint64_t nf = bal(e < 4) & (mask_le(kCountLanes) & ~1ull);
+                const uint64_t nfAll = bal(e < 4);
+                const uint64_t nf = nfAll & (mask_le(kCountLanes) & ~1ull);
+                if constexpr (CW) {
+                    // the first backward word with a difference ends the catch-up,
+                    // unless the bound (at most 62 < 4 kCatchWords) does so first
+                    const uint64_t nb = nfAll & kBackLanes;
+                    if (nb) {
+                        const uint32_t f = (uint32_t)__builtin_ctzll(nb);
+                        back = min(4 * (f - (kCountLanes + 1)) + rdlane(e, (int)f), maxb);
+                    } else {
+                        back = maxb;
+                    }
+                }
                 if (nf) {
                     const uint32_t f = (uint32_t)__builtin_ctzll(nf);
                     mc = 4 * (f - 1) + rdlane(e, (int)f);
@@ -348,6 +410,8 @@
                     if (kFastMargin && fastEndS == 0 && op + (n - ipe) + (n - ipe) / 255 + kFastOutSlack <= cap)
                         fastEndS = fastEndV;   // (b) holds from here to the block's end
                     sw = !fail && ipe < fastEndS;   // (fastEndS < mflimitP1)
+                    // (every later ip of the phase is at or above this ipe)
+                    if constexpr (kFastCatchW) sw = sw && ipe >= fastBegS;
                 }
             }
             sBase = ipe + 1;

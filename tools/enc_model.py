@@ -189,9 +189,24 @@ FAST_SPAN_MAX = 1016   # encode_block_v5: kFastSpanMax, kFastEndGap, kFastOutSla
 FAST_END_GAP = 1280
 FAST_OUT_SLACK = 64
 COUNT_LANES = 32
+CATCH_WORDS = 16      # kCatchWords: the lanes behind the count lanes load the 64 bytes below cd / ip as words
+FAST_BEG = 65536 + 4 * CATCH_WORDS   # kFastBeg
+RING = 2048           # kSR
 
 
-def encode_xchg(s, cap, phases=None):
+def back_from_words(s, ip, cd, maxb):
+    """the fast body's catch-up under LZ4MT_FAST_WINDOW bit 16: backward lane i
+    holds the words at cd - 4(i+1) and ip - 4(i+1); its equal bytes, counted
+    from the word's high end, are clz(x) >> 3 (4 when x = 0); the first lane
+    with fewer than 4 ends the catch-up unless the bound does so first"""
+    for i in range(CATCH_WORDS):
+        x = rd32(s, cd - 4 * (i + 1)) ^ rd32(s, ip - 4 * (i + 1))
+        if x:
+            return min(4 * i + ((32 - x.bit_length()) >> 3), maxb)
+    return maxb
+
+
+def encode_xchg(s, cap, phases=None, catch_words=False):
     """phases (a dict, optional): also runs encode_block_v5's phase rules
     (general -> fast -> general) beside the parse and asserts, at every
     window of the fast phase, that what the kernel's fast body drops has the
@@ -211,9 +226,26 @@ def encode_xchg(s, cap, phases=None):
     lane in fast windows), cont1_stop_lanes[L] (stops per lane in the first
     continuation window after a fast exit), fast_exits_redo (fast windows
     left without a stop after a tag alias, the exit that redoes the table
-    writes)."""
+    writes).
+    catch_words=True: the rules of LZ4MT_FAST_WINDOW bits 16 and 32 as well
+    (the kernel's default build; without it, the build of bits 1 + 2 + 4 + 8).
+    The phase is entered only after a match that ends at or above FAST_BEG,
+    and at every stop of a fast window the model asserts what the fast body
+    folds: the catch-up bound min(ip - anchor, cd) is w - 1, at most 62, the
+    candidate lies 64 bytes or more into the block, and the catch-up read
+    from the 16 backward words equals the byte loop's.  The model carries the
+    source ring's base (SrcRing::cover) and asserts at every pending store of
+    a fast window that the literals end inside the ring, so that the store's
+    in-ring test is its lower bound alone.  Counted: catch_full[back] (stops
+    of fast windows whose catch-up ate the whole literal run, back = w - 1),
+    catch_part[back] (back < w - 1), fast_store_total[min(total, 130)] and
+    fast_store_left_ring (pending stores of fast windows by sequence length,
+    and those whose literals had left the ring)."""
     n = len(s)
     fast = False
+    fast_beg = FAST_BEG if catch_words else 0
+    ring_b = 0     # SrcRing::B
+    pend = None    # the pending sequence: (anchor, lit, total)
     fast_end_v = n - FAST_END_GAP if n > FAST_END_GAP else 0
     assert 65547 <= n <= 1 << 22
     bound = n + n // 255 + 16
@@ -221,7 +253,8 @@ def encode_xchg(s, cap, phases=None):
     fast_end_s = 0 if limited else fast_end_v   # 0: output safety (b) not established yet
     if phases is not None:
         phases.update(fast_windows=0, general_windows=0, entries=0, wide_general=0,
-                      fast_stop_lanes=[0] * 64, cont1_stop_lanes=[0] * 64, fast_exits_redo=0)
+                      fast_stop_lanes=[0] * 64, cont1_stop_lanes=[0] * 64, fast_exits_redo=0,
+                      catch_full=[0] * 64, catch_part=[0] * 64, fast_store_total=[0] * 131, fast_store_left_ring=0)
     j1, span_hi = 65, 61   # the kernel's window state beside sPos + poff(k0), k0 and s0 = step(k0)
     after_fast_exit = False   # this window is the first continuation window after a fast exit
     T = [(tag_ht(rd32(s, 0)) << POSB)] * 4096 + [0] * 64
@@ -263,6 +296,21 @@ def encode_xchg(s, cap, phases=None):
             else:
                 phases["general_windows"] += 1
                 phases["wide_general"] += min(p[63], mfl) + 8 - lo > 1024
+        # the ring's advance at the window's head (not in a wide window), then
+        # the pending sequence's store (the kernel: in the round trip's
+        # shadow, or behind a window without a stop; once per sequence)
+        lo_w = p[0] if mode != 0 else p[2]
+        hi_w = min(p[63], mfl) + 8
+        if hi_w - lo_w <= 1024 and hi_w > ring_b + RING:
+            ring_b = (hi_w - RING + 511) & ~511
+        if pend is not None:
+            pa, pl, pt = pend
+            if fast and catch_words:
+                assert pa + pl <= ring_b + RING, (sPos, pa, pl, ring_b)   # the in-ring test's upper bound
+                if phases is not None:
+                    phases["fast_store_total"][min(pt, 130)] += 1
+                    phases["fast_store_left_ring"] += pa < ring_b
+            pend = None
         w0 = [rd32(s, min(p[L], n - 8)) for L in range(64)]
         h = [h5(rd64(s, min(p[L], n - 8))) for L in range(64)]
         mark = [(p[L] | (tag_ht(w0[L]) << POSB)) & 0xFFFFFFFF for L in range(64)]
@@ -334,6 +382,12 @@ def encode_xchg(s, cap, phases=None):
         back = 0
         while back < maxb and s[ip - back - 1] == s[cd - back - 1]:
             back += 1
+        if fast and catch_words:   # what the fast body folds (bit 16)
+            assert ip >= FAST_BEG and cd >= 4 * CATCH_WORDS, (ip, cd)
+            assert maxb == w - 1 <= 62 and back <= 62, (ip, w, maxb)
+            assert back == back_from_words(s, ip, cd, w - 1), (ip, cd, w, back)
+            if phases is not None:
+                phases["catch_full" if back == w - 1 else "catch_part"][back] += 1
         lim = matchlimit - (ip + 4)
         mc = 0
         while mc < lim and s[ip + 4 + mc] == s[cd + 4 + mc]:
@@ -358,6 +412,7 @@ def encode_xchg(s, cap, phases=None):
             seq += b"\xff" * (mlExt - 1) + bytes([(mcf - 15) % 255])
         out += seq
         op += len(seq)
+        pend = (anchor, lit, len(seq))
         ipe = ip + 4 + mc
         anchor = ipe
         if fast:
@@ -365,7 +420,7 @@ def encode_xchg(s, cap, phases=None):
         else:
             if fast_end_s == 0 and op + (n - ipe) + (n - ipe) // 255 + FAST_OUT_SLACK <= cap:
                 fast_end_s = fast_end_v
-            fast = ipe < fast_end_s
+            fast = fast_beg <= ipe < fast_end_s
             if fast and phases is not None:
                 phases["entries"] += 1
         if ipe >= mfl:
@@ -402,6 +457,67 @@ def literal_run_sweep(n, seed):
         out += out[a:a + k]
         r = (r + 1) % 200
     return bytes(out[:n])
+
+
+CATCH_SLOT = 34_000   # two slots are out of a candidate's range, one is inside it
+
+
+def catch_up_cases():
+    """(b, f) of the catch-up units: b bytes of catch-up behind f fresh
+    bytes.  f = 0: the catch-up eats the literal run whole (back = w - 1,
+    b = 0 is a stop on the TEST lane); f > 0: it ends on a differing byte
+    (back < w - 1).  The stop's lane is w = f + b + 1 <= 63."""
+    full = [(b, 0) for b in range(62)]
+    part = [(b, 1 + (7 * b) % (62 - b)) for b in range(62)] + [(0, 62), (3, 1), (4, 1), (5, 1), (7, 50)]
+    return full + part
+
+
+def catch_up_units(n, seed, units):
+    """A block of zero runs (long single matches, few table inserts) holding,
+    per unit (b, f), three occurrences one slot apart: U0 = a 66-byte body;
+    U1 = the body and 8 bytes t1 behind it, a match of U0 that ends at the
+    body's end E (positions inside a match are never inserted, E - 2 is, by
+    the next window's INSERT lane); P = f fresh bytes, the body's last b + 2
+    bytes and t1.  At P the body's inner positions find U0, two slots back and
+    out of range, or nothing; position E - 2's entry is found and the match
+    catches up b bytes, to a differing fresh byte or to the previous match's
+    end.  Whether a unit's table entries survive the inserts in between is
+    left to the seed: callers assert the coverage they need.  Behind the
+    slots: literal runs of 58 .. 61, 125 and 200 bytes before a short match
+    (sequences of 62 .. 65, 129 and 204 bytes), each behind a zero run
+    longer than the source ring."""
+    rnd = random.Random(seed)
+
+    def nz(k):
+        return bytes(rnd.randrange(1, 256) for _ in range(k))
+
+    buf = bytearray(n)
+    groups = n // CATCH_SLOT - 2
+    per = -(-len(units) // groups)
+    stride = CATCH_SLOT // per
+    assert groups >= 1 and stride >= 720, (groups, per, stride)
+    for i, (b, f) in enumerate(units):
+        g, j = divmod(i, per)
+        body, t1 = nz(66), nz(8)
+        fresh = nz(f)
+        while f and fresh[-1] == body[-(b + 3)]:
+            fresh = nz(f)
+        at = g * CATCH_SLOT + j * stride
+        buf[at + 100:at + 166] = body
+        at += CATCH_SLOT
+        buf[at + 266:at + 340] = body + t1
+        at += CATCH_SLOT
+        probe = fresh + body[-(b + 2):] + t1
+        buf[at + 440:at + 440 + len(probe)] = probe
+    at = (groups + 2) * CATCH_SLOT
+    for lit in (58, 59, 60, 61, 125, 200, 59, 60, 61, 125):
+        at += 2400
+        run = nz(lit)
+        tail = run[:8] + bytes([run[8] ^ 0x55 or 1])
+        assert at + lit + 9 + 1500 < n, n
+        buf[at:at + lit + 9] = run + tail
+        at += lit + 9
+    return bytes(buf)
 
 
 def long_search_input(n, run, seed):
