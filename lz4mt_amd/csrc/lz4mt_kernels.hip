@@ -641,19 +641,10 @@ typedef __attribute__((address_space(3))) uint64_t l_u64;
 constexpr uint32_t kSR = 2048;        // source ring bytes
 // forward-count words the v5 round trip loads per side (the first 4 * this
 // many bytes after the minimum match; longer matches take 256-byte rounds)
-#ifndef LZ4MT_COUNT_LANES
-#define LZ4MT_COUNT_LANES 32
-#endif
-constexpr uint32_t kCountLanes = LZ4MT_COUNT_LANES;
-// catch-up bytes the round trip loads per side (the bytes just before ip
-// and before the candidate); longer catch-ups take 64-byte rounds
-#ifndef LZ4MT_CATCH_LANES
-#define LZ4MT_CATCH_LANES 64
-#endif
-constexpr uint32_t kCatchLanes = LZ4MT_CATCH_LANES;
-static_assert(kCatchLanes >= 1 && kCatchLanes <= 64, "catch-up lanes");
-constexpr uint64_t kCatchMask = kCatchLanes >= 64 ? ~0ull : (1ull << kCatchLanes) - 1ull;
-static_assert(kCountLanes >= 1 && kCountLanes <= 63, "count lanes");
+// (32 count words and 64 catch-up bytes, a byte per lane just before ip and
+// before the candidate, against 16 words and 16 / 8 bytes:
+// profiles/r03g_encoder_ab_catch_count.txt)
+constexpr uint32_t kCountLanes = 32;
 constexpr uint32_t kSRMirror = 64;    // ring[kSR .. kSR+64) mirrors ring[0 .. 64)
 // ds_mskor_rtn_b32 on two LDS dwords (one position half, one tag byte): each
 // word becomes (word & ~mask) | data; returns the old words
@@ -858,21 +849,16 @@ __device__ __forceinline__ uint32_t pend_byte(const SeqLayout<R8>& e, uint32_t x
 // stays selects (no load sunk into a branch) and the store waits only on the
 // counter of its own load: LDS (ring, the common case) never waits on the
 // round-trip loads in flight.
-// FS (the fast body of encode_block_v5, LZ4MT_FAST_WINDOW bit 32):
-//   kPendRingLo   the caller has advanced the ring past the literals' end
-//                 (V.cover(hi), hi above the window's sBase and the literals
-//                 below it), so "in the ring" is the lower bound alone;
-//   kPendNoBytes  timing builds only (LZ4MT_EXP_NO_PEND_BYTES): no byte
-//                 rounds at all, the output is wrong.
-constexpr int kPendRingLo = 1, kPendNoBytes = 4;
-template <bool R8, int FS = 0>
+// FS (the fast body of encode_block_v5): ring lower bound only.  The caller
+// has advanced the ring past the literals' end (V.cover(hi), hi above the
+// window's sBase and the literals below it), so "in the ring" is the lower
+// bound alone.
+template <bool R8, bool FS = false>
 __device__ __forceinline__ void store_pend(const PendSeq& p, const SrcRing& V, g_cu8* __restrict__ s,
                                            g_u8* __restrict__ d) {
-    if constexpr ((FS & kPendNoBytes) != 0) return;
     const uint32_t L = laneid();
     // (inRing: evaluated where it is used, V.B is not re-read in between)
-#define LZ4MT_PEND_IN_RING \
-    ((FS & kPendRingLo) ? p.anchor >= V.B : p.anchor >= V.B && p.anchor + p.lit <= V.B + kSR)
+#define LZ4MT_PEND_IN_RING (FS ? p.anchor >= V.B : p.anchor >= V.B && p.anchor + p.lit <= V.B + kSR)
     // the layout in VALU (uniform values in VGPRs): the scalar unit is the
     // CU's busiest port in the encoder window, the vector ALU is not
     PendSeq q = p;
@@ -1025,18 +1011,11 @@ struct SimdPrio {
         const uint32_t fin = (uint32_t)t0 + (uint32_t)((float)(uint32_t)(now - t0) / (frac > 1e-3f ? frac : 1e-3f));
         const uint32_t L = laneid();
         if (L == 0) __hip_atomic_store(g_simdFinish + base + slot, fin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#if LZ4MT_EXP_CUPRIO   // rank among the CU's waves (4 SIMDs x 16 slots), priority = rank / 2
-        const uint32_t cb = base & ~63u;
-        const uint32_t e = __hip_atomic_load(g_simdFinish + cb + L, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const bool live = cb + L != base + slot && (int32_t)(e - (uint32_t)now) > 0;
-        const uint32_t rank = (uint32_t)__builtin_popcountll(bal(live && (int32_t)(e - fin) < 0)) >> 1;
-#else
         const uint32_t e = L < 16 ? __hip_atomic_load(g_simdFinish + base + L, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                                   : 0u;
         // live SIMD-mates projected to finish before this wave
         const bool live = L < 16 && L != slot && (int32_t)(e - (uint32_t)now) > 0;
         const uint32_t rank = (uint32_t)__builtin_popcountll(bal(live && (int32_t)(e - fin) < 0));
-#endif
         if (rank >= 3) __builtin_amdgcn_s_setprio(3);
         else if (rank == 2) __builtin_amdgcn_s_setprio(2);
         else if (rank == 1) __builtin_amdgcn_s_setprio(1);
@@ -1112,10 +1091,7 @@ __device__ int32_t encode_block_v5(g_cu8* __restrict__ s, uint32_t n, g_u8* __re
     uint32_t tickShift = 31;
     if (prioOn) {
         prio.start();
-#ifndef LZ4MT_EXP_PRIO_SHIFT
-#define LZ4MT_EXP_PRIO_SHIFT 7
-#endif
-        tickShift = (31 - __builtin_clz(blen)) - LZ4MT_EXP_PRIO_SHIFT;   // a check every 1/128 of the block
+        tickShift = (31 - __builtin_clz(blen)) - 7;   // a check every 1/128 of the block
     }
     const uint32_t capL = limited ? cap : 0xFFFFFFFFu;   // one SGPR for the per-sequence margin test
     const uint32_t mflimitP1 = n - kMfLimit + 1;
@@ -1131,11 +1107,12 @@ __device__ int32_t encode_block_v5(g_cu8* __restrict__ s, uint32_t n, g_u8* __re
     auto store_pending = [&]() {
         // remainders mod 256 without a multiply: B4 -2.6 %, B5 -1.4 %; on the
         // byU32 encoder +0.5 % (profiles/r06/r06pq_quarter_rate_ab.txt)
-#ifndef LZ4MT_EXP_R8ALL
         store_pend<U16 || P17>(pe, V, s, d);
-#else
-        store_pend<LZ4MT_EXP_R8ALL != 0>(pe, V, s, d);
-#endif
+        havePe = false;
+    };
+    // the fast body's: the in-ring test is the ring's lower bound alone, (d) below
+    [[maybe_unused]] auto store_pending_fast = [&]() {
+        store_pend<U16 || P17, true>(pe, V, s, d);
         havePe = false;
     };
     // window: lane 0 INSERT insPos, lane 1 TEST testPos, lane L >= 2 SEARCH
@@ -1149,14 +1126,23 @@ __device__ int32_t encode_block_v5(g_cu8* __restrict__ s, uint32_t n, g_u8* __re
     uint32_t spanHi = 61;
     uint32_t nextSweep = 32768;   // P17
     // ---- two phases (the frame encoder's instantiation): general -> fast ->
-    // general.  The fast phase runs the same windows without the work whose
-    // result is fixed away from the block's end:
+    // general.  The general body is the whole window loop: any window state,
+    // the block's end, the output margins.  The fast body runs one window per
+    // iteration, the first window after a match (k0 = 0, s0 = 1, j1 = 65,
+    // mode = 1, spanHi = 61: constants there, sBase the only window state it
+    // carries), without the work whose result is fixed away from the block's
+    // ends.  It is entered after a match that ends in
+    // [fastBegS, fastEndS) and left after one that ends at or past fastEndS
+    // (one compare, in place of the general ipe >= mflimitP1), or by a window
+    // without a stop (sBase += 62): the general body resumes that search from the
+    // continuation state (k0 = 62) written once behind the fast loop, and
+    // the phase is entered again after its match.  Four invariants:
     //   (a) end distance.  Every fast window starts at sBase <= fastEndS =
-    //       n - kFastEndGap with spanHi <= kFastSpanMax (so s0 <= 16), hence
-    //       for every lane p + step <= sBase + spanHi + 17 < mflimitP1
-    //       (liveM = ~3 | roleM, tmk = 0, wTerm false, hi = sHi + 8) and for
-    //       every stop ip + 4 + 4 kCountLanes + 8 <= matchlimit (no clamp of
-    //       the round trip's addresses or of the first count round binds).
+    //       n - kFastEndGap and probes up to sBase + 61 with step 1, hence
+    //       for every lane p + step <= sBase + 62 < mflimitP1 (every SEARCH
+    //       lane live, tmk = 0, wTerm false, hi = sBase + 69) and for every
+    //       stop ip + 4 + 4 kCountLanes + 8 <= matchlimit (no clamp of the
+    //       round trip's addresses or of the first count round binds).
     //   (b) output safety.  With R = n - anchor the input still to encode,
     //       fastEndS stays 0 until  op + R + R / 255 + kFastOutSlack <= cap.
     //       A sequence (lit literals, match 4 + mcf) takes lit + 4 + mcf input
@@ -1168,93 +1154,58 @@ __device__ int32_t encode_block_v5(g_cu8* __restrict__ s, uint32_t n, g_u8* __re
     //       lit + mcf + lit / 255 + 11 (after the match length) and R +
     //       R / 255 + 2 (last literals) bytes after op; R >= lit + mcf + 4,
     //       so none can fire: the fast phase carries no margin test.
-    //   The wide window (hi - lo > 1024) needs spanHi > 1016: never in a fast
-    //   window.  The phase is left before a window that (a) or the span bound
-    //   does not cover: after a match by ipe >= fastEndS (in place of the
-    //   general ipe >= mflimitP1), after a continuation by the new sBase and
-    //   spanHi.  It is entered after a match only (spanHi = 61).
-    //   (c) begin distance (bit 16).  The phase is entered only after a match
-    //       with ipe >= fastBegS = o0 + 65536 + 64, and ipe never falls, so
-    //       every stop of the phase has ip >= ipe >= 65536 + 64 and its
-    //       candidate, at most 65535 below, cd >= 65 > 64: the 16 backward
-    //       words at cd - 4 .. cd - 64 (and those below ip) lie inside the
-    //       block -- also in block 0 of a buffer and in a chunk of
-    //       k_encode_batch that starts on its allocation's first byte.  A
-    //       fast window is the first after a match: anchor = sBase - 1, lane
-    //       w probes sBase + w - 2 (the TEST lane, w = 1, sBase - 1), so
+    //   The window is never wide (hi - lo = 72, far below 1024), so the fast
+    //   body has no wide test and no reads of hash inputs from global memory.
+    //   (c) begin distance.  The phase is entered only after a match with
+    //       ipe >= fastBegS = o0 + 65536 + 64, and ipe never falls, so every
+    //       stop of the phase has ip >= ipe >= 65536 + 64 and its candidate,
+    //       at most 65535 below, cd >= 65 > 64: the 16 backward words at
+    //       cd - 4 .. cd - 64 (and those below ip) lie inside the block --
+    //       also in block 0 of a buffer and in a chunk of k_encode_batch that
+    //       starts on its allocation's first byte.  A fast window is the
+    //       first after a match: anchor = sBase - 1, lane w probes
+    //       sBase + w - 2 (the TEST lane, w = 1, sBase - 1), so
     //       ip - anchor = w - 1 <= 62 < cd and lz4's catch-up bound
-    //       min(ip - anchor, cd - 0) is w - 1: 64 bytes below the stop
-    //       always reach it, the loops for longer catch-ups cannot run.
-    //   (d) ring bound (bit 32).  A fast window is never wide, so its
-    //       V.cover(hi) has run and hi <= V.B + kSR; the pending literals end
-    //       at or below the previous stop, below sBase < hi: the store's
-    //       in-ring test is anchor >= V.B alone.
-    // LZ4MT_FAST_WINDOW (A/B builds): 0 the one general loop (also
-    // -DLZ4MT_NO_FAST_WINDOW); 1 the fast phase without the end predicates
-    // and clamps; + 2 without the margin test, entered once (b) holds;
-    // + 4 without the wide test; + 8 first windows only: the fast body runs
-    // the first window after a match with its window state (k0 = 0, s0 = 1,
-    // j1 = 65, mode = 1, spanHi = 61) folded into constants, and a window
-    // without a stop leaves the phase: the general body resumes the search
-    // from the continuation state (k0 = 62) and the phase is entered again
-    // after its match.  Without bit 8 the loop is the one of bits 1 + 2 + 4.
-    // + 16 (needs 8): the catch-up bytes come as 16 words below cd / ip in
-    // the round trip's idle count lanes, the bound is w - 1, no catch-up
-    // loops, and the phase begins at fastBegS, (c); + 32 (needs 4 and 8): the
-    // pending store's in-ring test is its lower bound alone, (d).  Without
-    // bits 16 and 32 the encoder object is the one of 15.
-#ifndef LZ4MT_FAST_WINDOW
-#ifdef LZ4MT_NO_FAST_WINDOW
-#define LZ4MT_FAST_WINDOW 0
+    //       min(ip - anchor, cd - 0) is w - 1: the catch-up bytes come as
+    //       words in the round trip's idle lanes, 64 bytes below the stop
+    //       always reach the bound, and there are no loops for longer
+    //       catch-ups.
+    //   (d) ring bound.  A fast window is never wide, so its V.cover(hi) has
+    //       run and hi <= V.B + kSR; the pending literals end at or below the
+    //       previous stop, below sBase < hi: the store's in-ring test is
+    //       anchor >= V.B alone (store_pending_fast).
+    // -DLZ4MT_NO_FAST_WINDOW (the baseline of A/B builds): the one general
+    // loop in every instantiation.
+#ifndef LZ4MT_NO_FAST_WINDOW
+    constexpr bool kFastT = !ST && !U16 && !SPLIT && !LINK && !P17 && !PUB && !XH && !DUP;
 #else
-#define LZ4MT_FAST_WINDOW 63
-#endif
-#endif
-    constexpr bool kFastT = (LZ4MT_FAST_WINDOW & 1) && !ST && !U16 && !SPLIT && !LINK && !P17 && !PUB && !XH && !DUP;
-    constexpr bool kFastMargin = (LZ4MT_FAST_WINDOW & 2) != 0, kFastNoWide = (LZ4MT_FAST_WINDOW & 4) != 0;
-    constexpr bool kFastFirst = (LZ4MT_FAST_WINDOW & 8) != 0;
-    constexpr bool kFastCatchW = kFastFirst && (LZ4MT_FAST_WINDOW & 16) != 0;
-    // (the ring bound needs the window's V.cover(hi) to have run: no wide windows)
-    [[maybe_unused]] constexpr bool kFastRingLo = kFastFirst && kFastNoWide && (LZ4MT_FAST_WINDOW & 32) != 0;
-#ifdef LZ4MT_EXP_NO_PEND_BYTES   // timing builds only: the fast body's pending store writes no bytes
-    constexpr int kFastStoreFS = kPendNoBytes;
-#else
-    constexpr int kFastStoreFS = kFastRingLo ? kPendRingLo : 0;
-#endif
-    // the fast body's pending store is store_pend<kPendR8, kFastStoreFS>
-#ifndef LZ4MT_EXP_R8ALL
-    [[maybe_unused]] constexpr bool kPendR8 = U16 || P17;
-#else
-    [[maybe_unused]] constexpr bool kPendR8 = LZ4MT_EXP_R8ALL != 0;
+    constexpr bool kFastT = false;
 #endif
     // first window after a match: lane L's position minus sBase (INSERT
     // sBase - 3, TEST sBase - 1, SEARCH sBase + L - 2)
     const uint32_t firstOff = L == 0 ? (uint32_t)-3 : (L == 1 ? (uint32_t)-1 : L - 2);
-    // kFastCatchW, the round trip's word of lane L, as an offset from cd and
+    // the fast body's round trip: the word of lane L as an offset from cd and
     // from ip: lane 0 the verify word, lanes 1 .. kCountLanes the forward
     // count words, the kCatchWords lanes behind them the words BELOW cd / ip
     // (lane kCountLanes + 1 + i: bytes -4(i+1) .. -4i-1), the rest lane 0's
     constexpr uint32_t kCatchWords = 16;
-#ifndef LZ4MT_CATCH_GATE
-#define LZ4MT_CATCH_GATE 1
-#endif
-    [[maybe_unused]] constexpr bool kCatchGate = LZ4MT_CATCH_GATE != 0;
     static_assert(kCountLanes + 1 + kCatchWords <= 64, "catch-up word lanes");
     [[maybe_unused]] constexpr uint64_t kBackLanes = ((1ull << kCatchWords) - 1ull) << (kCountLanes + 1);
     uint32_t rtOff = 0;
-    if constexpr (kFastCatchW && kFastT)
+    if constexpr (kFastT)
         rtOff = L <= kCountLanes ? 4 * L : (L <= kCountLanes + kCatchWords ? 4 * kCountLanes - 4 * L : 0u);
     // ipe >= fastBegS: every stop of the phase has ip >= 65536 + 64, so its
     // candidate cd >= ip - 65535 lies 64 bytes or more into the block
     constexpr uint32_t kFastBeg = kDistMax + 1 + 4 * kCatchWords;
     [[maybe_unused]] const uint32_t fastBegS = o0 + kFastBeg;
-    constexpr uint32_t kFastSpanMax = 1016;   // hi - lo = spanHi + 8 <= 1024
-    // sBase + kFastSpanMax + 17 (step) + 4 + 4 kCountLanes + 8 < n - kMfLimit, with room to spare
+    // (a): sBase + 61 (last probe) + 1 (step) + 4 + 4 kCountLanes + 8 <
+    // n - kMfLimit.  The gap has room to spare: it was sized for windows of
+    // any span up to 1016 (profiles/r07), and the first-window body keeps it
     constexpr uint32_t kFastEndGap = 1280;
-    static_assert(kFastSpanMax + 17 + 4 + 4 * kCountLanes + 8 + kMfLimit + 64 <= kFastEndGap, "fast phase end distance");
+    static_assert(61 + 1 + 4 + 4 * kCountLanes + 8 + kMfLimit + 64 <= kFastEndGap, "fast phase end distance");
     constexpr uint32_t kFastOutSlack = 64;
     const uint32_t fastEndV = n > o0 + kFastEndGap ? n - kFastEndGap : 0u;
-    uint32_t fastEndS = (!kFastMargin || !limited) ? fastEndV : 0u;   // 0: (b) not established yet
+    uint32_t fastEndS = !limited ? fastEndV : 0u;   // 0: (b) not established yet
     // the window loop, once per phase (lz4mt_v5_window.inc: windows until the
     // block is done or the phase changes); without a fast phase, one pass
     for (;;) {
@@ -2166,10 +2117,7 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
 // ---------------------------------------------------------------------------
 // Decoder
 // ---------------------------------------------------------------------------
-#ifndef LZ4MT_DEC_RING
-#define LZ4MT_DEC_RING 16384
-#endif
-constexpr int32_t kRing = LZ4MT_DEC_RING;   // LDS history ring (bytes; A/B: -DLZ4MT_DEC_RING=8192 / 32768)
+constexpr int32_t kRing = 16384;   // LDS history ring (bytes; 8192 / 32768: profiles/r03_decoder_ring_ab.txt)
 static_assert((kRing & (kRing - 1)) == 0 && kRing >= 4096, "history ring: a power of two");
 constexpr int32_t kInWin = 2048;   // LDS input window (bytes)
 constexpr int32_t kFlush = 1024;   // ring -> HBM flush granule (64 lanes x 16 B)
@@ -2178,13 +2126,10 @@ constexpr int32_t kFlush = 1024;   // ring -> HBM flush granule (64 lanes x 16 B
 // into the table, so a hop is one dependent ds_read_u16
 constexpr int32_t kNxOff = kInWin + 128;      // inside the win[] allocation
 constexpr uint32_t kNxPast = 1024, kNxDead = 1026;
-// far matches of a batch whose bytes load together (LZ4MT_FAR_TAB, A/B):
-// App. F batches hold ~31 sequences, ~8 of them far (offset > the ring);
-// the rest are loaded one at a time
-#ifndef LZ4MT_FAR_TAB
-#define LZ4MT_FAR_TAB 8
-#endif
-constexpr int kFarTab = LZ4MT_FAR_TAB;
+// far matches of a batch whose bytes load together: App. F batches hold ~31
+// sequences, ~8 of them far (offset > the ring); the rest are loaded one at a
+// time (8 / 12 / 16 entries: profiles/r03h_decoder_fartab_ab.txt)
+constexpr int kFarTab = 8;
 // A batch's far-match parameters are read straight from their lanes (s_ff1
 // over the far mask + v_readlane) instead of a rank-ordered LDS table read
 // back by broadcast, so no far load waits on an LDS round trip (k_decode
@@ -4269,11 +4214,6 @@ __global__ void __launch_bounds__(1024) k_frame_scan(const int32_t* __restrict__
     if (t == 1023) recOff[nBlocks] = part[1023];
 }
 
-// chunks per thread in flight in the assembly's middle loop (A/B)
-#ifndef LZ4MT_ASM_UNROLL
-#define LZ4MT_ASM_UNROLL 1
-#endif
-
 __global__ void __launch_bounds__(256) k_frame_assemble(const uint8_t* __restrict__ src, const uint8_t* __restrict__ slots,
                                                         uint64_t srcSize, uint32_t blockSize,
                                                         const int32_t* __restrict__ csize,
@@ -4302,9 +4242,10 @@ __global__ void __launch_bounds__(256) k_frame_assemble(const uint8_t* __restric
     const uint64_t head = A0 - Da, tailStart = E0 - Da;
     for (uint64_t i = t; i < head; i += 256) D[i] = sp[i];
     for (uint64_t i = tailStart + t; i < L; i += 256) D[i] = sp[i];
-    // middle: 16-B aligned destination chunks gathered from the source
+    // middle: 16-B aligned destination chunks gathered from the source, one
+    // chunk per thread in flight (4 were no faster, profiles/r03n_xxh32_ab.txt)
     const uint64_t nchunks = (E0 - A0) >> 4;
-#pragma unroll LZ4MT_ASM_UNROLL
+#pragma unroll 1
     for (uint64_t j = t; j < nchunks; j += 256) {
         const uint64_t so = head + 16 * j;                 // source byte offset of this chunk
         g_cu32* q = (g_cu32*)(sp + (so & ~3ull));

@@ -4,24 +4,22 @@
 // lambda or a helper template: the instantiations without a fast phase
 // then compile to the code they had as one loop, and the loop-carried state
 // stays in the enclosing function's registers.
-// FIRST (the fast body under LZ4MT_FAST_WINDOW bit 8): every window of the
-// phase is the first window after a match, so k0 = 0, s0 = 1, j1 = 65,
-// mode = 1 and spanHi = 61 are constants here and not loop state; a window
-// without a stop leaves the phase with the continuation state written out.
+// FAST: every window of the phase is the first window after a match, so
+// k0 = 0, s0 = 1, j1 = 65, mode = 1 and spanHi = 61 are constants here and
+// not loop state (sBase is the only window state the fast body carries); the
+// catch-up bytes come as words in the round trip's idle count lanes, bounded
+// by w - 1; there is no margin test and no wide window; the pending store
+// tests the ring's lower bound only; a window without a stop leaves the
+// phase, and the continuation state is written once, behind the loop.
 {
     constexpr bool FAST = V5_FAST;
-    constexpr bool FIRST = FAST && kFastFirst;
-    // CW (LZ4MT_FAST_WINDOW bit 16): the catch-up bytes come as words in the
-    // round trip's idle count lanes; STF (bit 32): the leaner pending store
-    constexpr bool CW = FAST && kFastCatchW;
-    constexpr bool STF = FIRST && kFastStoreFS != 0;
     bool sw = false;   // leave this phase
-    bool fcont = false;   // FIRST: the phase was left by a window without a stop
+    bool fcont = false;   // FAST: the phase was left by a window without a stop
     // ONE exit and no continue: the structurizer then needs no flow
     // variables and the loop-carried state stays in place across windows
     while (!done && !sw) {
-      // windows without a stop (continuations) loop here, inside: the
-      // match-path state (anchor, op, pe) is not touched by them
+      // general body: windows without a stop (continuations) loop here,
+      // inside: the match-path state (anchor, op, pe) is not touched by them
       uint32_t w, ip, cd, maxb, cw, iw, bi, bc;
       bool wTerm;
       do {
@@ -40,23 +38,23 @@
         // j < 62 and the step s0 < 2^24: a full-rate 24-bit multiply (lanes 0
         // and 1 wrap j, but take the INSERT / TEST position below)
         uint32_t p = sBase + __umul24(j, s0) + (uint32_t)max(jx, 0);
-        const uint32_t step = FIRST ? 1u : s0 + (jx >= 0 ? 1u : 0u);
-        const uint32_t sHi = sBase + (FIRST ? 61u : spanHi);
-        const bool insOn = FIRST ? true : mode != 0;
-        const uint32_t insPos = !FIRST && mode == 2 ? o0 : sBase - 3, testPos = sBase - 1;
+        const uint32_t step = FAST ? 1u : s0 + (jx >= 0 ? 1u : 0u);
+        const uint32_t sHi = sBase + (FAST ? 61u : spanHi);
+        const bool insOn = FAST ? true : mode != 0;
+        const uint32_t insPos = !FAST && mode == 2 ? o0 : sBase - 3, testPos = sBase - 1;
         p = L == 0 ? insPos : (L == 1 ? testPos : p);
-        // (FIRST, j1 = 65 > j and s0 = 1: all of the above is one add of the
+        // (FAST, j1 = 65 > j and s0 = 1: all of the above is one add of the
         // lane's constant offset, -3, -1 or L - 2)
-        if constexpr (FIRST) p = sBase + firstOff;
+        if constexpr (FAST) p = sBase + firstOff;
         // lane predicates as wave masks (SALU), turned back into per-lane
         // conditions with inverse_ballot (the mask is the select's condition):
         // no 0/1 materialisation chains.  Lane 0 / 1's bits come straight
         // from the mode (2: INSERT only, 1: both, 0: neither)
-        const uint64_t roleM = FIRST ? 3ull : (uint64_t)((0x130u >> (4 * mode)) & 3u);
+        const uint64_t roleM = FAST ? 3ull : (uint64_t)((0x130u >> (4 * mode)) & 3u);
         // (fast phase: every SEARCH lane is live and none is the block's last)
         const uint64_t liveM = FAST ? ~3ull | roleM : (bal(p <= mflimitP1) & ~3ull) | roleM;
         const uint64_t tmk = FAST ? 0ull : bal(p + step > mflimitP1) & liveM & ~3ull;
-        const bool live = FIRST ? true : __builtin_amdgcn_inverse_ballot_w64(liveM);
+        const bool live = FAST ? true : __builtin_amdgcn_inverse_ballot_w64(liveM);
         const bool term = FAST ? false : __builtin_amdgcn_inverse_ballot_w64(tmk);
         const uint32_t lo = insOn ? insPos : sBase;
         const uint32_t hi = (FAST || sHi < mflimitP1 ? sHi : mflimitP1) + 8;
@@ -64,7 +62,8 @@
         // two if-regions and no else: the ring read is issued on both paths
         // (wasted, harmless, in the rare wide case), so the common path
         // carries no structurizer flow variable
-        const bool wide = FAST && kFastNoWide ? false : hi - lo > 1024;
+        // (fast phase: hi - lo = 72, never wide)
+        const bool wide = FAST ? false : hi - lo > 1024;
         if constexpr (kPrioT) {   // the check rides on the ring's advance (every 512 B of input or more)
             if (!wide && hi > V.B + kSR) {
                 const uint32_t oldB = V.B;
@@ -196,53 +195,48 @@
                 if (w < 64 && !wTerm) {
                     ip = rdlane(p, (int)w);
                     cd = rdlane(cand, (int)w);
-                    if constexpr (CW) {
+                    // every side from global memory: reading the near side(s)
+                    // from the LDS ring when they lie in it was slower
+                    // (profiles/r03j_encoder_ring_rt_ab.txt, r04s_encoder_ip_ring_ab.txt)
+                    if constexpr (FAST) {
                         // first window after a match: anchor = sBase - 1 and lane w
                         // probes sBase + w - 2 (the TEST lane sBase - 1), so
                         // ip - anchor = w - 1, and cd >= 64 > w - 1 (fastBegS)
                         maxb = w - 1;
-                    } else {   // catch-up bound: lz4's lowLimit for the candidate's side
-                        const uint32_t lowL = !LINK ? 0u : (cd >= o0 ? lk.lowIn : lk.lowDict);
-                        maxb = w == 1 ? 0u : min(ip - anchor, cd > lowL ? cd - lowL : 0u);
-                    }
-                    if constexpr (CW) {
                         // lane 0: verify word; lanes 1 .. kCountLanes: count words;
                         // the next kCatchWords lanes: the 64 bytes below cd / ip as
                         // words (cd >= 64: inside the block); the rest repeat lane
-                        // 0's address: one add of the lane's constant offset.  A
-                        // backward lane whose word lies wholly beyond the bound
-                        // (4 i >= maxb) also repeats lane 0's address, so fewer
-                        // candidate-side lines are touched; whatever it then
-                        // reports, 4 i + e >= maxb and the bound decides
-                        // (LZ4MT_CATCH_GATE=0, A/B builds: every backward lane loads)
-                        const uint32_t ro =
-                            !kCatchGate || (int32_t)rtOff >= -(int32_t)((maxb + 3) & ~3u) ? rtOff : 0u;
+                        // 0's address: one add of the lane's constant offset (and
+                        // ip + 4 kCountLanes < last4: no clamp).  A backward lane
+                        // whose word lies wholly beyond the bound (4 i >= maxb)
+                        // also repeats lane 0's address, so fewer candidate-side
+                        // lines are touched; whatever it then reports,
+                        // 4 i + e >= maxb and the bound decides
+                        const uint32_t ro = (int32_t)rtOff >= -(int32_t)((maxb + 3) & ~3u) ? rtOff : 0u;
                         cw = xld4(cd + ro);
                         iw = gld4u(s + (ip + ro));
                     } else {
-                    // lane 0: verify word; lanes 1 .. kCountLanes: count words; the
-                    // rest repeat lane 0's address (no further lines touched)
-                    const bool cOn = L <= kCountLanes;
-                    const uint32_t ci = cOn ? cd + 4 * L : cd, ii = cOn ? ip + 4 * L : ip;
-                    const bool bOn = L < maxb && L < kCatchLanes;
-                    // every side from global memory: reading the near side(s)
-                    // from the LDS ring when they lie in it was slower
-                    // (profiles/r03j_encoder_ring_rt_ab.txt, r04s_encoder_ip_ring_ab.txt)
-                    // (fast phase: ip + 4 kCountLanes < last4, no clamp)
-                    cw = xld4(FAST || ci < last4 ? ci : last4);
-                    iw = gld4u(s + (FAST || ii < last4 ? ii : last4));
-                    uint32_t bix = bOn ? ip - L - 1 : o0, bcx = bOn ? cd - L - 1 : o0;   // (o0: a byte of the block itself)
-                    asm volatile("" : "+v"(bix), "+v"(bcx));   // 32-bit offsets, SGPR-base loads
-                    bi = s[bix];
-                    bc = xld1(bcx);
+                        // catch-up bound: lz4's lowLimit for the candidate's side
+                        const uint32_t lowL = !LINK ? 0u : (cd >= o0 ? lk.lowIn : lk.lowDict);
+                        maxb = w == 1 ? 0u : min(ip - anchor, cd > lowL ? cd - lowL : 0u);
+                        // lane 0: verify word; lanes 1 .. kCountLanes: count words; the
+                        // rest repeat lane 0's address (no further lines touched)
+                        const bool cOn = L <= kCountLanes;
+                        const uint32_t ci = cOn ? cd + 4 * L : cd, ii = cOn ? ip + 4 * L : ip;
+                        // catch-up bytes: lane L the byte L + 1 below ip and below cd
+                        // (L < 64 always holds, but the compiler does not know it:
+                        // without the compare every encoder kernel's code moves)
+                        const bool bOn = L < maxb && L < 64;
+                        cw = xld4(ci < last4 ? ci : last4);
+                        iw = gld4u(s + (ii < last4 ? ii : last4));
+                        uint32_t bix = bOn ? ip - L - 1 : o0, bcx = bOn ? cd - L - 1 : o0;   // (o0: a byte of the block itself)
+                        asm volatile("" : "+v"(bix), "+v"(bcx));   // 32-bit offsets, SGPR-base loads
+                        bi = s[bix];
+                        bc = xld1(bcx);
                     }
                     if (havePe) {
-                        if constexpr (STF) {
-                            store_pend<kPendR8, kFastStoreFS>(pe, V, s, d);
-                            havePe = false;
-                        } else {
-                            store_pending();
-                        }
+                        if constexpr (FAST) store_pending_fast();
+                        else store_pending();
                     }
                     table_writes(w, false, ip);   // in the round trip's shadow; redone if w moves
                     twDone = true;
@@ -261,12 +255,8 @@
             }
         }
         if (havePe) {
-            if constexpr (STF) {
-                store_pend<kPendR8, kFastStoreFS>(pe, V, s, d);
-                havePe = false;
-            } else {
-                store_pending();
-            }
+            if constexpr (FAST) store_pending_fast();
+            else store_pending();
         }
         // no stop in the window (w == 64): every insert stays, nothing to put
         // back -- unless an alias moved the stop here after the lanes past the
@@ -274,9 +264,10 @@
         if (!twDone && (!XCHG || w < 64 || twRedo)) table_writes(w, wTerm, rdlane(p, (int)(w < 64 ? w - 1 : 63)));
         STAMP_ADD(1, ts);
         STAMP_ADD(2, ts);
-        if constexpr (FIRST) {
+        if constexpr (FAST) {
             // no stop: the search goes on in the general body, which resumes
-            // it from the continuation state written behind this loop
+            // it from the continuation state written behind this loop (about
+            // 1 window in 20 is a continuation)
             if (w == 64) {
                 sBase += 62;
                 fcont = true;
@@ -289,11 +280,8 @@
             j1 = (k0 < 65 ? 65u : ((k0 - 1) & ~63u) + 65) - k0;
             mode = 0;
             spanHi = 61 * s0 + (61 > j1 ? 61 - j1 : 0u);
-            // the next window needs the general body (about 1 window in 20
-            // is a continuation: the test is off the sequence chain)
-            if constexpr (FAST) sw = spanHi > kFastSpanMax || sBase > fastEndS;
         }
-      } while (!FIRST && w == 64 && !(FAST && sw));
+      } while (!FAST && w == 64);
         if (FAST && w == 64) {
             // phase left inside a search: the general loop resumes it
         } else if (wTerm) {
@@ -302,46 +290,38 @@
             // ---- catch-up (backwards) and LZ4_count (forwards from ip + 4).
             // bi/bc are consumed on every path, so no load of this window is
             // left pending into the next window's round trip.
-            uint64_t fm = 0;
             uint32_t back = 0;
-            if constexpr (!CW) {
-            asm volatile("" ::"v"(bi), "v"(bc));
-            fm = ~(bal(L < maxb) & bal(bi == bc)) & kCatchMask;
-            if (kCatchLanes < 64 && fm == 0) {   // every loaded byte matched, the limit lies beyond them
-                back = kCatchLanes;
-                const uint32_t kb = back + L + 1;
-                const bool on = kb <= maxb;
-                fm = ~bal(on && s[on ? ip - kb : o0] == xld1(on ? cd - kb : o0));
-            }
-            while (fm == 0 && back + 64 < maxb) {   // catch-up longer than 64 bytes
-                back += 64;
-                const uint32_t kb = back + L + 1;
-                const bool on = kb <= maxb;
-                fm = ~bal(on && s[on ? ip - kb : o0] == xld1(on ? cd - kb : o0));
-            }
-            back = fm ? back + (uint32_t)__builtin_ctzll(fm) : maxb;
+            if constexpr (!FAST) {
+                asm volatile("" ::"v"(bi), "v"(bc));
+                uint64_t fm = ~(bal(L < maxb) & bal(bi == bc));
+                while (fm == 0 && back + 64 < maxb) {   // catch-up longer than 64 bytes
+                    back += 64;
+                    const uint32_t kb = back + L + 1;
+                    const bool on = kb <= maxb;
+                    fm = ~bal(on && s[on ? ip - kb : o0] == xld1(on ? cd - kb : o0));
+                }
+                back = fm ? back + (uint32_t)__builtin_ctzll(fm) : maxb;
             }
             const uint32_t lim = matchlimit - (ip + kMinMatch);
             uint32_t mc;
             {
-                const uint32_t rel = 4 * L - 4;
                 const uint32_t x = cw ^ iw;
                 uint32_t e;
-                if constexpr (CW) {
+                if constexpr (FAST) {
                     // equal bytes from the word's near end: its low end in a
                     // forward lane, its high end in a backward one
+                    // (lim >= 4 kCountLanes: no clamp)
                     const bool bk = __builtin_amdgcn_inverse_ballot_w64(kBackLanes);
                     e = x ? ((bk ? (uint32_t)__builtin_clz(x) : (uint32_t)__builtin_ctz(x)) >> 3) : 4u;
                 } else {
+                    const uint32_t rel = 4 * L - 4;
                     e = x ? ((uint32_t)__builtin_ctz(x) >> 3) : 4u;
-                }
-                if constexpr (!FAST) {   // (fast phase: lim >= 4 kCountLanes)
                     e = min(e, lim - rel);
                     e = rel < lim ? e : 0u;   // (lane 0's e is masked out below)
                 }
                 const uint64_t nfAll = bal(e < 4);
                 const uint64_t nf = nfAll & (mask_le(kCountLanes) & ~1ull);
-                if constexpr (CW) {
+                if constexpr (FAST) {
                     // the first backward word with a difference ends the catch-up,
                     // unless the bound (at most 62 < 4 kCatchWords) does so first
                     const uint64_t nb = nfAll & kBackLanes;
@@ -384,14 +364,14 @@
                 // 1.9.3's limitedOutput margins; both hold whenever
                 // op + 2 (lit + mcf) + 16 <= cap, so the exact test runs rarely
                 // (fast phase: condition (b) above holds, neither can fire)
-                if constexpr (!(FAST && kFastMargin)) {
+                if constexpr (!FAST) {
                     if (op + 2 * (lit + mcf) + 16 > capL) {
                         fail = (w != 1 && op + 1 + lit + 8 + lit / 255 > cap) ||
                                (op + 1 + litExt + lit + 2 + 6 + (mcf + 240) / 255 > cap);
                     }
                 }
                 pe.op = op;
-                havePe = FAST && kFastMargin ? true : !fail;
+                havePe = FAST ? true : !fail;
                 if constexpr (PUB) {   // every sequence before this one has been stored: [0, op) is final
                     if ((op ^ (op + 1 + litExt + lit + 2 + mlExt)) >> kPubShift) publish_progress(pub, op);
                 }
@@ -402,20 +382,19 @@
             if constexpr (FAST) {
                 // one compare, as in the general phase: past fastEndS the
                 // general loop decides whether the block is done
-                if constexpr (kFastMargin) sw = ipe >= fastEndS;
-                else sw = fail || ipe >= fastEndS;
+                sw = ipe >= fastEndS;
             } else {
                 done = fail || ipe >= mflimitP1;
                 if constexpr (kFastT) {
-                    if (kFastMargin && fastEndS == 0 && op + (n - ipe) + (n - ipe) / 255 + kFastOutSlack <= cap)
+                    if (fastEndS == 0 && op + (n - ipe) + (n - ipe) / 255 + kFastOutSlack <= cap)
                         fastEndS = fastEndV;   // (b) holds from here to the block's end
                     sw = !fail && ipe < fastEndS;   // (fastEndS < mflimitP1)
-                    // (every later ip of the phase is at or above this ipe)
-                    if constexpr (kFastCatchW) sw = sw && ipe >= fastBegS;
+                    // (c): every later ip of the phase is at or above this ipe
+                    sw = sw && ipe >= fastBegS;
                 }
             }
             sBase = ipe + 1;
-            if constexpr (!FIRST) {
+            if constexpr (!FAST) {
                 mode = 1;
                 k0 = 0;
                 s0 = 1;
@@ -425,10 +404,10 @@
             STAMP_ADD(4, ts);
         }
     }
-    // FIRST: the window state the general body resumes from, written once per
+    // FAST: the window state the general body resumes from, written once per
     // phase change and not per sequence -- the second window of a search
     // (k0 = 62: the step rises at j = 3), or the first window after a match
-    if constexpr (FIRST) {
+    if constexpr (FAST) {
         k0 = fcont ? 62u : 0u;
         j1 = fcont ? 3u : 65u;
         mode = fcont ? 0u : 1u;

@@ -1,12 +1,12 @@
 """The fast body's catch-up from words and its leaner pending store (DESIGN
-4.1, LZ4MT_FAST_WINDOW bits 16 and 32) in the lane model (tools/enc_model.py,
+4.1, catch-up from words and one-sided ring test) in the lane model (tools/enc_model.py,
 encode_xchg(..., catch_words=True)).
 
-Under bit 16 the fast body reads the 64 bytes below the candidate and below
+With the catch-up from words the fast body reads the 64 bytes below the candidate and below
 the stop as 16 words in lanes the count round leaves idle, takes the bound of
 the catch-up as w - 1 (the stop's lane) and has no loop for longer catch-ups;
 the phase is entered only after a match that ends at or above 65536 + 64.
-Under bit 32 the pending store's in-ring test is its lower bound alone.  The
+With the one-sided ring test the pending store's in-ring test is its lower bound alone.  The
 model asserts at every stop of a fast window that min(ip - anchor, cd) is
 w - 1 <= 62, that the candidate lies 64 bytes or more into the block and that
 the catch-up from the words is the byte loop's, and at every pending store of
@@ -80,7 +80,7 @@ def test_store_lengths_around_one_round_and_literals_out_of_the_ring():
 
 
 def test_without_the_new_rules_the_model_is_the_parents():
-    """catch_words=False: the phase rules of bits 1 + 2 + 4 + 8 (entered from
+    """catch_words=False: the phase rules of first windows alone (entered from
     the block's first match on), same bytes"""
     data = enc_model.catch_up_units(N, SEEDS[0], enc_model.catch_up_cases())
     cap = N + N // 255 + 16

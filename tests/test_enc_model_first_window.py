@@ -1,5 +1,5 @@
-"""The first-window fast phase of encode_block_v5 (DESIGN 4.1, LZ4MT_FAST_WINDOW
-bit 8) in the lane model (tools/enc_model.py, encode_xchg(..., phases)): a fast
+"""The first-window fast phase of encode_block_v5 (first windows
+only) in the lane model (tools/enc_model.py, encode_xchg(..., phases)): a fast
 window is the first window after a match, with k0 = 0, s0 = 1, j1 = 65,
 mode = 1 and spanHi = 61 folded into constants, and a window without a stop
 leaves the phase.  The model asserts at every fast window that the folded

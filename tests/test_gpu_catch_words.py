@@ -1,5 +1,5 @@
 """The fast body's catch-up from words, its phase entry at 65536 + 64 and its
-leaner pending store (DESIGN 4.1, LZ4MT_FAST_WINDOW bits 16 and 32) on the
+leaner pending store (catch-up from words, one-sided ring test) on the
 GPU.  Every comparison is the encoder's block against the oracle's (LZ4 1.9.3
 restated) through lz4mtHipCompressBlock, which runs the frame encoder's own
 instantiation (k_encode; 300 000 B blocks, about 5 ms each), with the

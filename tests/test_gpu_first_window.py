@@ -1,5 +1,5 @@
-"""The frame encoder's first-window fast phase (DESIGN 4.1, LZ4MT_FAST_WINDOW
-bit 8) on the GPU.
+"""The frame encoder's first-window fast phase (first windows
+only) on the GPU.
 
 The fast body of encode_block_v5 runs the first window after a match only,
 with the window state folded into constants (lane positions sBase + c(L),

@@ -185,7 +185,7 @@ def tag_ht(w0):
     return ((((w0 << 24) * 889523592379) & 0xFFFFFFFFFFFFFFFF) >> (52 - (32 - POSB))) & ((1 << (32 - POSB)) - 1)
 
 
-FAST_SPAN_MAX = 1016   # encode_block_v5: kFastSpanMax, kFastEndGap, kFastOutSlack, kCountLanes
+FAST_SPAN_MAX = 1016   # the span kFastEndGap was sized for; encode_block_v5: kFastEndGap, kFastOutSlack, kCountLanes
 FAST_END_GAP = 1280
 FAST_OUT_SLACK = 64
 COUNT_LANES = 32
@@ -195,7 +195,7 @@ RING = 2048           # kSR
 
 
 def back_from_words(s, ip, cd, maxb):
-    """the fast body's catch-up under LZ4MT_FAST_WINDOW bit 16: backward lane i
+    """the fast body's catch-up from words in the idle lanes: backward lane i
     holds the words at cd - 4(i+1) and ip - 4(i+1); its equal bytes, counted
     from the word's high end, are clz(x) >> 3 (4 when x = 0); the first lane
     with fewer than 4 ends the catch-up unless the bound does so first"""
@@ -214,7 +214,7 @@ def encode_xchg(s, cap, phases=None, catch_words=False):
     hi, of the round trip's addresses or of the first count round binding,
     no wide window, neither margin test firing.  Counts the windows and
     phase entries into it.
-    A fast window is a first window after a match (LZ4MT_FAST_WINDOW bit 8):
+    A fast window is a first window after a match (first windows only):
     the kernel's fast body folds the window state k0 = 0, s0 = 1, j1 = 65,
     mode = 1, spanHi = 61 into constants, and a window without a stop leaves
     the phase with the continuation state written as constants.  The model
@@ -227,8 +227,9 @@ def encode_xchg(s, cap, phases=None, catch_words=False):
     continuation window after a fast exit), fast_exits_redo (fast windows
     left without a stop after a tag alias, the exit that redoes the table
     writes).
-    catch_words=True: the rules of LZ4MT_FAST_WINDOW bits 16 and 32 as well
-    (the kernel's default build; without it, the build of bits 1 + 2 + 4 + 8).
+    catch_words=True: the rules of the catch-up from words and of the
+    one-sided ring test as well (the kernel's fast body; without it, the fast
+    body of first windows with the byte-wise catch-up).
     The phase is entered only after a match that ends at or above FAST_BEG,
     and at every stop of a fast window the model asserts what the fast body
     folds: the catch-up bound min(ip - anchor, cd) is w - 1, at most 62, the
@@ -382,7 +383,7 @@ def encode_xchg(s, cap, phases=None, catch_words=False):
         back = 0
         while back < maxb and s[ip - back - 1] == s[cd - back - 1]:
             back += 1
-        if fast and catch_words:   # what the fast body folds (bit 16)
+        if fast and catch_words:   # what the fast body folds (catch-up from words)
             assert ip >= FAST_BEG and cd >= 4 * CATCH_WORDS, (ip, cd)
             assert maxb == w - 1 <= 62 and back <= 62, (ip, w, maxb)
             assert back == back_from_words(s, ip, cd, w - 1), (ip, cd, w, back)
