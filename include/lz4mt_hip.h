@@ -250,12 +250,45 @@ uint64_t lz4mtHipShardBodyBytes(uint64_t n, const Lz4MtStreamDescriptor* sd, voi
  * LZ4MT_RESULT_BAD_ARG: a null array with nChunks > 0 (d_dstCaps may be
  * null for compress only), maxChunkBytes above the maximum; then
  * LZ4MT_RESULT_ERROR without a HIP device or on a launch error; else
- * LZ4MT_RESULT_OK (nChunks == 0 launches nothing). */
+ * LZ4MT_RESULT_OK (nChunks == 0 launches nothing).
+ *
+ * Compress with a level (lz4mtHipCompressBatchEx).  level < 3: exactly
+ * lz4mtHipCompressBatch; the workspace is ignored and may be NULL.
+ * level >= 3: LZ4-HC.  Bytes and d_outSizes[i] are those of
+ * lz4mtHipCompressBlock(src, dst, d_srcSizes[i], d_dstCaps[i], level), i.e.
+ * LZ4_compressHC2_limitedOutput of lz4 1.9.3 (levels 3..9 the hashChain
+ * parser, 10..12 the optimal parser, above 12 = 12) -- 0 when the block does
+ * not fit; d_dstCaps == NULL as above.  The blocks are ordinary LZ4 blocks:
+ * lz4mtHipDecompressBatch decodes them.  The memory contract and the refused
+ * chunks (LZ4MT_HIP_BATCH_BAD_CHUNK) are the same as for the fast codec.
+ * One wavefront parses one chunk from end to end, whatever its size: the
+ * frame engine's split parse of 1 and 4 MiB blocks is not used here.
+ * Workspace: device scratch in slots sized by maxChunkBytes (2 bytes per
+ * source byte for the hash chain; from level 10 up a 57 KiB price table as
+ * well); slot k serves the k-th chunk of a round.
+ * lz4mtHipCompressBatchWorkspaceSize(maxChunkBytes, nChunks, level) is
+ * min(nChunks, LZ4MT_HIP_BATCH_HC_SLOTS) slots -- with nChunks = 1, one slot,
+ * which is never 0 at level >= 3 -- and 0 at level < 3.  The call accepts any
+ * 256-byte-aligned workspace of at least one slot, uses
+ * min(workspaceSize / slot, LZ4MT_HIP_BATCH_HC_SLOTS) slots and runs
+ * ceil(nChunks / slots) rounds of two launches on `stream`: a smaller
+ * workspace costs time, never bytes.  The workspace must not be used by
+ * anything else until the call has run; its contents need not be kept.
+ * Still asynchronous and graph-capturable: no allocation, no
+ * synchronisation, no host read of the arrays, no environment variable.
+ * LZ4MT_RESULT_BAD_ARG as above, then (level >= 3 and nChunks > 0) for a
+ * workspace that is NULL, not 256-byte aligned or smaller than one slot. */
 #define LZ4MT_HIP_BATCH_MAX_CHUNK (4u << 20)
 #define LZ4MT_HIP_BATCH_BAD_CHUNK INT32_MIN
+#define LZ4MT_HIP_BATCH_HC_SLOTS 16384u
 Lz4MtResult lz4mtHipCompressBatch(const void* const* d_srcPtrs, const uint32_t* d_srcSizes, uint32_t maxChunkBytes,
                                   uint32_t nChunks, void* const* d_dstPtrs, const uint32_t* d_dstCaps,
                                   int32_t* d_outSizes, void* stream);
+uint64_t lz4mtHipCompressBatchWorkspaceSize(uint32_t maxChunkBytes, uint32_t nChunks, int level);
+Lz4MtResult lz4mtHipCompressBatchEx(const void* const* d_srcPtrs, const uint32_t* d_srcSizes, uint32_t maxChunkBytes,
+                                    uint32_t nChunks, void* const* d_dstPtrs, const uint32_t* d_dstCaps,
+                                    int32_t* d_outSizes, int level, void* d_workspace, uint64_t workspaceSize,
+                                    void* stream);
 Lz4MtResult lz4mtHipDecompressBatch(const void* const* d_srcPtrs, const uint32_t* d_srcSizes, uint32_t nChunks,
                                     void* const* d_dstPtrs, const uint32_t* d_dstCaps, int32_t* d_outSizes,
                                     void* stream);

@@ -28,6 +28,7 @@ __all__ = [
     "device_count", "stream_bound", "frame_records", "xxh32_chunks", "frame_header", "shard_workspace",
     "shard_pack_bound", "shard_reset", "shard_encode", "shard_pack", "shard_unpack", "shard_assemble", "shard_body_bytes",
     "batch_compress_bound", "compress_batch", "decompress_batch", "BATCH_MAX_CHUNK", "BATCH_BAD_CHUNK",
+    "batch_compress_workspace", "BATCH_HC_SLOTS",
 ]
 
 lib = _abi.load()
@@ -162,6 +163,7 @@ def _check_dev(t, name):
 # ---------------------------------------------------------------------------
 BATCH_MAX_CHUNK = _abi.BATCH_MAX_CHUNK
 BATCH_BAD_CHUNK = _abi.BATCH_BAD_CHUNK
+BATCH_HC_SLOTS = _abi.BATCH_HC_SLOTS
 
 
 def batch_compress_bound(n):
@@ -169,11 +171,23 @@ def batch_compress_bound(n):
     return compress_bound(n)
 
 
-def _batch(fn_name, srcs, caps, null_caps, max_chunk, stream):
+def batch_compress_workspace(max_chunk, n, level, device=None):
+    """Scratch for compress_batch / lz4mtHipCompressBatchEx at ``level`` over
+    ``n`` chunks of at most ``max_chunk`` bytes: a uint8 tensor of
+    lz4mtHipCompressBatchWorkspaceSize bytes (empty below level 3).  The call
+    accepts any workspace of at least one slot (``n = 1``) and runs more rounds
+    with fewer slots."""
+    nbytes = int(lib.lz4mtHipCompressBatchWorkspaceSize(int(max_chunk), int(n), int(level)))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device or "cuda")
+
+
+def _batch(fn_name, srcs, caps, null_caps, max_chunk, stream, level=0, workspace=None):
     """The common part of compress_batch / decompress_batch: one backing
     allocation for the outputs (each at a 16-byte-aligned offset, ``cap``
     bytes long), the four descriptor arrays built on the host and uploaded
-    in one copy, one library call.  Everything is issued on ``stream``."""
+    in one copy, one library call.  Everything is issued on ``stream``.
+    ``level`` >= 3 (compress only): lz4mtHipCompressBatchEx, its workspace
+    allocated here on the call's stream unless one is given."""
     n = len(srcs)
     dev = srcs[0].device if n else torch.device("cuda", torch.cuda.current_device())
     if stream is None:
@@ -209,7 +223,14 @@ def _batch(fn_name, srcs, caps, null_caps, max_chunk, stream):
         fn = getattr(lib, fn_name)
         st = ctypes.c_void_p(ts.cuda_stream)
         cap_arg = ctypes.c_void_p(None if null_caps else d_cap)
-        if max_chunk is None:
+        if level >= 3:
+            if workspace is None:
+                workspace = batch_compress_workspace(max_chunk, n, level, device=dev)
+            fn_name = "lz4mtHipCompressBatchEx"
+            r = lib.lz4mtHipCompressBatchEx(ctypes.c_void_p(d_src), ctypes.c_void_p(d_sz), max_chunk, n,
+                                            ctypes.c_void_p(d_dst), cap_arg, ctypes.c_void_p(sizes.data_ptr()),
+                                            level, ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), st)
+        elif max_chunk is None:
             r = fn(ctypes.c_void_p(d_src), ctypes.c_void_p(d_sz), n, ctypes.c_void_p(d_dst), cap_arg,
                    ctypes.c_void_p(sizes.data_ptr()), st)
         else:
@@ -220,15 +241,23 @@ def _batch(fn_name, srcs, caps, null_caps, max_chunk, stream):
         return [back[o:o + c] for o, c in zip(offs, caps)], sizes
 
 
-def compress_batch(chunks, caps=None, stream=None):
+def compress_batch(chunks, caps=None, stream=None, level=0, workspace=None):
     """lz4mtHipCompressBatch: every tensor of ``chunks`` (contiguous uint8 on
     one HIP device, slices at any offset included, at most 4 MiB each) as an
     independent raw LZ4 block, in one launch.  ``caps``: a capacity per chunk
     (default: the bound of each size).  Returns ``(outs, sizes)``: ``outs[i]``
     a ``caps[i]``-byte view of one backing allocation, ``sizes`` the int32
     device tensor of block sizes (0: does not fit its capacity).  Does not
-    synchronise: ``chunks`` must stay alive until ``stream`` has run the call."""
+    synchronise: ``chunks`` must stay alive until ``stream`` has run the call.
+    ``level`` >= 3: LZ4-HC through lz4mtHipCompressBatchEx (one wave per chunk
+    and a launch pair per round); ``workspace``: a uint8 device tensor of at
+    least one slot (batch_compress_workspace), kept alive and untouched until
+    the call has run -- by default one of the full size is allocated on the
+    call's stream."""
     chunks = list(chunks)
+    level = int(level)
+    if workspace is not None and level >= 3:
+        _check_dev(workspace, "workspace")
     for i, c in enumerate(chunks):
         _check_dev(c, f"chunks[{i}]")
     big = max((c.numel() for c in chunks), default=0)
@@ -236,11 +265,11 @@ def compress_batch(chunks, caps=None, stream=None):
         raise ValueError(f"a chunk of {big} bytes exceeds the batch maximum of {BATCH_MAX_CHUNK}")
     if caps is None:
         return _batch("lz4mtHipCompressBatch", chunks, [batch_compress_bound(c.numel()) for c in chunks], True, big,
-                      stream)
+                      stream, level, workspace)
     caps = [int(c) for c in caps]
     if len(caps) != len(chunks) or any(c < 0 or c >= 1 << 32 for c in caps):
         raise ValueError("caps: one capacity of 0 .. 2^32 - 1 per chunk")
-    return _batch("lz4mtHipCompressBatch", chunks, caps, False, big, stream)
+    return _batch("lz4mtHipCompressBatch", chunks, caps, False, big, stream, level, workspace)
 
 
 def decompress_batch(blocks, caps, stream=None):

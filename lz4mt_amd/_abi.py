@@ -34,6 +34,7 @@ Result = type("Result", (), {name: i for i, name in enumerate(RESULT_NAMES)})
 # lz4mt_hip.h section 5 (batched block operators)
 BATCH_MAX_CHUNK = 4 << 20
 BATCH_BAD_CHUNK = -(1 << 31)
+BATCH_HC_SLOTS = 16384
 
 
 class Lz4MtFlg(ctypes.Structure):
@@ -94,6 +95,9 @@ PROTOTYPES = {
     "lz4mtHipCompressBound": (c_int, [c_int]),
     "lz4mtHipDecompressBlock": (c_int, [c_void_p, c_void_p, c_int, c_int]),
     "lz4mtHipCompressBatch": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lz4mtHipCompressBatchWorkspaceSize": (c_uint64, [c_uint32, c_uint32, c_int]),
+    "lz4mtHipCompressBatchEx": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_int,
+                                        c_void_p, c_uint64, c_void_p]),
     "lz4mtHipDecompressBatch": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lz4mtHipFrameBound": (c_uint64, [c_uint64, SD_P]),
     "lz4mtHipCompressWorkspaceSize": (c_uint64, [c_uint64, SD_P]),

@@ -24,6 +24,34 @@ constexpr int kDecodeOutputTooSmall = INT32_MIN;   // physical slot smaller than
 constexpr uint32_t kBatchMaxChunk = 4u << 20;
 constexpr int32_t kBatchBadChunk = INT32_MIN;
 
+#ifdef __HIP__
+// One chunk's descriptor, read at the uniform index blockIdx.x (scalar
+// loads); bad: LZ4MT_HIP_BATCH_BAD_CHUNK, nothing written.  The one
+// definition of a refused chunk for the fast kernels (lz4mt_kernels.hip) and
+// the LZ4-HC ones (lz4mt_hc.hip).
+struct BatchChunk {
+    const __attribute__((address_space(1))) uint8_t* s;
+    __attribute__((address_space(1))) uint8_t* d;
+    uint32_t n, cap;
+    bool bad;
+};
+__device__ __forceinline__ BatchChunk batch_chunk(const uint8_t* const* __restrict__ srcPtrs,
+                                                  const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
+                                                  uint8_t* const* __restrict__ dstPtrs,
+                                                  const uint32_t* __restrict__ dstCaps) {
+    const uint32_t i = blockIdx.x;
+    BatchChunk c;
+    c.n = srcSizes[i];
+    const uint8_t* sp = srcPtrs[i];
+    uint8_t* dp = dstPtrs[i];
+    c.s = (const __attribute__((address_space(1))) uint8_t*)sp;
+    c.d = (__attribute__((address_space(1))) uint8_t*)dp;
+    c.cap = dstCaps ? dstCaps[i] : c.n + c.n / 255 + 16;   // lz4mtHipCompressBound
+    c.bad = c.n > maxChunk || !dp || (reinterpret_cast<uintptr_t>(dp) & 15) != 0 || (!sp && c.n != 0);
+    return c;
+}
+#endif
+
 // Per-block record of a parsed frame (device-resident, one per block).
 struct BlockRec {
     uint64_t offset;     // payload offset inside the frame
@@ -186,6 +214,21 @@ uint32_t hc_split_sub();
 uint64_t hc_split_bytes(uint64_t nBlocks, uint32_t blockSize);
 uint64_t hc_ws_bytes(uint64_t nBlocks, uint32_t blockSize, int level);   // splitWs size for a level
 uint32_t hc_attempts(int level);   // lz4hc nbSearches of a level (> 12 = 12)
+// The batched LZ4-HC (lz4mt_hip.h section 5, level >= 3): k_hc_prev_batch,
+// then k_encode_hc_batch (levels 3..9) or k_encode_hc_opt_batch (10 and up),
+// one wave per chunk.  Scratch comes in slots of hc_batch_slot_bytes(maxChunk,
+// level): the chunk's chain deltas and, from level 10 up, its price table;
+// slot k serves the k-th chunk of a round.  ws holds `slots` >= 1 of them
+// (256-byte aligned); the batch runs in ceil(nChunks / slots) rounds over
+// slices of the arrays, a launch pair each, so a slot's next user starts
+// after its previous one has ended.  kHcBatchSlots: the most slots a call
+// uses (and lz4mtHipCompressBatchWorkspaceSize asks for): 16 waves for each
+// of the 1024 SIMDs of an MI355X.
+constexpr uint32_t kHcBatchSlots = 16384;
+uint64_t hc_batch_slot_bytes(uint32_t maxChunk, int level);
+hipError_t launch_encode_hc_batch(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
+                                  uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps,
+                                  int32_t* outSizes, int level, uint8_t* ws, uint32_t slots, hipStream_t st);
 // -BD at level >= 3: segments [begin[k], end[k]) of src (begin >= -64 KiB),
 // blockSeg[b] = block b's segment; delta0 = chain scratch for src[0], with
 // 64 Ki entries before it.

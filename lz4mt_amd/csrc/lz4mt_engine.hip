@@ -553,6 +553,37 @@ extern "C" Lz4MtResult lz4mtHipCompressBatch(const void* const* d_srcPtrs, const
     return LZ4MT_RESULT_OK;
 }
 
+// The same with a level.  Below 3 it is lz4mtHipCompressBatch.  From 3 up:
+// LZ4-HC (lz4mt_hc.hip), scratch in slots of the caller's workspace, as many
+// rounds of a launch pair as the slots ask for (launch_encode_hc_batch) --
+// still nothing but launches on `stream`.
+static_assert(LZ4MT_HIP_BATCH_HC_SLOTS == kHcBatchSlots, "batch ABI");
+extern "C" uint64_t lz4mtHipCompressBatchWorkspaceSize(uint32_t maxChunkBytes, uint32_t nChunks, int level) {
+    if (level < 3) return 0;
+    return hc_batch_slot_bytes(maxChunkBytes, level) * std::min(nChunks, kHcBatchSlots);
+}
+
+extern "C" Lz4MtResult lz4mtHipCompressBatchEx(const void* const* d_srcPtrs, const uint32_t* d_srcSizes,
+                                               uint32_t maxChunkBytes, uint32_t nChunks, void* const* d_dstPtrs,
+                                               const uint32_t* d_dstCaps, int32_t* d_outSizes, int level,
+                                               void* d_workspace, uint64_t workspaceSize, void* stream) {
+    if (level < 3)
+        return lz4mtHipCompressBatch(d_srcPtrs, d_srcSizes, maxChunkBytes, nChunks, d_dstPtrs, d_dstCaps, d_outSizes,
+                                     stream);
+    if (nChunks && (!d_srcPtrs || !d_srcSizes || !d_dstPtrs || !d_outSizes)) return LZ4MT_RESULT_BAD_ARG;
+    if (maxChunkBytes > LZ4MT_HIP_BATCH_MAX_CHUNK) return LZ4MT_RESULT_BAD_ARG;
+    const uint64_t slot = hc_batch_slot_bytes(maxChunkBytes, level);
+    if (nChunks && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0 || workspaceSize < slot))
+        return LZ4MT_RESULT_BAD_ARG;
+    if (!have_device()) return LZ4MT_RESULT_ERROR;
+    if (nChunks == 0) return LZ4MT_RESULT_OK;
+    const uint32_t slots = (uint32_t)std::min<uint64_t>(workspaceSize / slot, kHcBatchSlots);
+    HIPCHK(launch_encode_hc_batch(reinterpret_cast<const uint8_t* const*>(d_srcPtrs), d_srcSizes, maxChunkBytes,
+                                  nChunks, reinterpret_cast<uint8_t* const*>(d_dstPtrs), d_dstCaps, d_outSizes, level,
+                                  static_cast<uint8_t*>(d_workspace), slots, static_cast<hipStream_t>(stream)));
+    return LZ4MT_RESULT_OK;
+}
+
 extern "C" Lz4MtResult lz4mtHipDecompressBatch(const void* const* d_srcPtrs, const uint32_t* d_srcSizes,
                                                uint32_t nChunks, void* const* d_dstPtrs, const uint32_t* d_dstCaps,
                                                int32_t* d_outSizes, void* stream) {

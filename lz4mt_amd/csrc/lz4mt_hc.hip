@@ -846,6 +846,84 @@ __global__ void __launch_bounds__(64) k_encode_hc_opt_g(const uint8_t* __restric
 }
 
 // ---------------------------------------------------------------------------
+// Batched block operator at level >= 3 (lz4mt_hip.h section 5,
+// lz4mtHipCompressBatchEx): chunk blockIdx.x of a round, an independent raw
+// block.  Source, size, destination and capacity come from device arrays
+// (batch_chunk: uniform index, scalar loads); the chunk's scratch is slot
+// blockIdx.x of the workspace: its chain deltas, then (levels >= 10) its
+// price table.  The device functions above already serve a caller's buffers:
+// the source is read by bytes (hc_chunk_load takes a dwordx4 only inside an
+// aligned chunk), the output is written by bytes below the cursor under
+// lz4hc's limitedOutput checks, so nothing is read outside [s, s + n) and
+// nothing is written at or beyond d + cap.
+// Chain entries: hc_prev_range writes dl[0 .. n - 4]; the parsers use dl[p]
+// only for positions p <= n - 12 (every search position is at most mflimit,
+// every candidate lies below it).  The chain-swap scan of HcBlock::wider
+// loads 64 links at a time, up to 63 entries past the last one it selects
+// (so up to entry n + 47): loaded, never selected, and inside the slot's
+// kHcBatchDeltaPad.  A slot's stale entries from an earlier round are
+// therefore never used.
+// As in k_encode_batch: no wait on another wave, no loop over chunks, no
+// atomics: a wave (a workgroup of k_hc_prev_batch) that runs ends.
+// ---------------------------------------------------------------------------
+constexpr uint64_t kHcBatchDeltaPad = 128;   // bytes after a slot's maxChunk deltas (64 entries)
+constexpr uint64_t hc_batch_delta_bytes(uint32_t maxChunk) {
+    return (2 * (uint64_t)maxChunk + kHcBatchDeltaPad + 255) & ~uint64_t(255);
+}
+
+// The chain of every chunk of the round, one workgroup per chunk.  The
+// refusal is workgroup-uniform (blockIdx.x only) and comes before the first
+// __syncthreads; hc_prev_range's early end for n < 4 is uniform as well.
+__global__ void __launch_bounds__(kPrevThreads) k_hc_prev_batch(const uint8_t* const* __restrict__ srcPtrs,
+                                                                const uint32_t* __restrict__ srcSizes,
+                                                                uint32_t maxChunk,
+                                                                uint8_t* const* __restrict__ dstPtrs,
+                                                                uint8_t* __restrict__ ws, uint64_t slotBytes) {
+    __shared__ uint32_t last[1u << kHashLog];
+    __shared__ uint8_t dd[4 * 1024];
+    __shared__ __attribute__((aligned(16))) uint32_t ring[2048];
+    const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, nullptr);
+    if (c.bad) return;   // a size above maxChunk would not fit the slot
+    hc_prev_range(c.s, c.n, (g_u16*)(ws + (uint64_t)blockIdx.x * slotBytes), (l_u32*)last, (l_u8*)dd, (l_u32*)ring);
+}
+
+// Levels 3..9: the hashChain parse of chunk blockIdx.x, one wave
+__global__ void __launch_bounds__(64) k_encode_hc_batch(const uint8_t* const* __restrict__ srcPtrs,
+                                                        const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
+                                                        uint8_t* const* __restrict__ dstPtrs,
+                                                        const uint32_t* __restrict__ dstCaps,
+                                                        int32_t* __restrict__ outSizes,
+                                                        const uint8_t* __restrict__ ws, uint64_t slotBytes,
+                                                        uint32_t maxAttempts) {
+    const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, dstCaps);
+    int32_t r = kBatchBadChunk;
+    if (!c.bad) {
+        HcBlock B{c.s, c.n, (g_cu16*)(ws + (uint64_t)blockIdx.x * slotBytes), maxAttempts, maxAttempts > 128};
+        r = encode_block_hc(B, c.d, c.cap);
+    }
+    if (laneid() == 0) outSizes[blockIdx.x] = r;
+}
+
+// Levels 10..12: the optimal parse of chunk blockIdx.x, one wave, the price
+// table after the slot's deltas (global memory, as k_encode_hc_opt_g's)
+__global__ void __launch_bounds__(64) k_encode_hc_opt_batch(const uint8_t* const* __restrict__ srcPtrs,
+                                                            const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
+                                                            uint8_t* const* __restrict__ dstPtrs,
+                                                            const uint32_t* __restrict__ dstCaps,
+                                                            int32_t* __restrict__ outSizes, uint8_t* ws,
+                                                            uint64_t slotBytes, uint64_t tableAt, uint32_t nbSearches,
+                                                            int32_t sufficientLen, int32_t fullUpdate) {
+    const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, dstCaps);
+    int32_t r = kBatchBadChunk;
+    if (!c.bad) {
+        uint8_t* slot = ws + (uint64_t)blockIdx.x * slotBytes;
+        HcBlock B{c.s, c.n, (g_cu16*)slot, nbSearches, true};   // pattern analysis always on
+        r = encode_block_hc_opt(B, c.d, c.cap, hc_opt_at(slot + tableAt, 0), sufficientLen, fullUpdate != 0);
+    }
+    if (laneid() == 0) outSizes[blockIdx.x] = r;
+}
+
+// ---------------------------------------------------------------------------
 // Split parse of large blocks.  A 4 MiB block is one serial hashChain parse
 // (k_encode_hc: 2048 waves for 8 GiB, latency-bound); here stream j of a
 // block starts its own parse at M_j = j * sub (j = 0: the block start) and
@@ -1195,6 +1273,44 @@ hipError_t launch_encode_hc(const uint8_t* src, uint64_t srcSize, uint32_t block
     hipLaunchKernelGGL(k_encode_hc, dim3(nBlocks), dim3(64), 0, st, src, srcSize, blockSize, slots, slotStride,
                        capOverride, (const uint16_t*)delta, att, csize, (const uint32_t*)nullptr);
     return hipGetLastError();
+}
+
+// One slot of the batched LZ4-HC's workspace: maxChunk chain deltas (+ the
+// pad the chain-swap scan may load), and from level 10 up one price table.
+// Never 0, a multiple of 256.
+uint64_t hc_batch_slot_bytes(uint32_t maxChunk, int level) {
+    const uint64_t table = (kOptBlockBytes + 255) & ~uint64_t(255);
+    return hc_batch_delta_bytes(maxChunk) + (level >= 10 ? table : 0);
+}
+
+// Rounds of at most `slots` chunks over slices of the arrays: chunk o + k of
+// a round uses slot k.  Stream order keeps a round's parse after its chains
+// and the next round's chains after this round's parse.  Nothing but
+// launches: no allocation, no synchronisation, no environment.
+hipError_t launch_encode_hc_batch(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
+                                  uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps,
+                                  int32_t* outSizes, int level, uint8_t* ws, uint32_t slots, hipStream_t st) {
+    if (level < 3 || slots == 0 || !ws) return hipErrorInvalidValue;
+    slots = std::min(slots, kHcBatchSlots);
+    const uint32_t att = hc_attempts(level);
+    const int lv = level > 12 ? 12 : level;
+    const int32_t tl = lv == 10 ? 64 : lv == 11 ? 128 : kOptNum, fu = lv == 12 ? 1 : 0;   // as launch_encode_hc
+    const uint64_t slotBytes = hc_batch_slot_bytes(maxChunk, level), tableAt = hc_batch_delta_bytes(maxChunk);
+    for (uint32_t o = 0; o < nChunks;) {
+        const uint32_t g = std::min(nChunks - o, slots);
+        const uint32_t* caps = dstCaps ? dstCaps + o : nullptr;
+        hipLaunchKernelGGL(k_hc_prev_batch, dim3(g), dim3(kPrevThreads), 0, st, srcPtrs + o, srcSizes + o, maxChunk,
+                           dstPtrs + o, ws, slotBytes);
+        if (lv >= 10)
+            hipLaunchKernelGGL(k_encode_hc_opt_batch, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, maxChunk,
+                               dstPtrs + o, caps, outSizes + o, ws, slotBytes, tableAt, att, tl, fu);
+        else
+            hipLaunchKernelGGL(k_encode_hc_batch, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, maxChunk,
+                               dstPtrs + o, caps, outSizes + o, (const uint8_t*)ws, slotBytes, att);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        o += g;
+    }
+    return hipSuccess;
 }
 
 }  // namespace lz4mt

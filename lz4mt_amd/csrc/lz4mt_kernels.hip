@@ -1547,29 +1547,8 @@ __global__ void __launch_bounds__(64) k_encode16(const uint8_t* __restrict__ src
 //     (encode_block's 8-byte flushes, of whole 512-byte granules below the
 //     cursor, need the destination's alignment, checked here per chunk).
 // No wait on another wave, no loop over chunks, no atomics: a wave that
-// runs ends.
-// One chunk's descriptor; bad: LZ4MT_HIP_BATCH_BAD_CHUNK, nothing written.
-struct BatchChunk {
-    g_cu8* s;
-    g_u8* d;
-    uint32_t n, cap;
-    bool bad;
-};
-__device__ __forceinline__ BatchChunk batch_chunk(const uint8_t* const* __restrict__ srcPtrs,
-                                                  const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
-                                                  uint8_t* const* __restrict__ dstPtrs,
-                                                  const uint32_t* __restrict__ dstCaps) {
-    const uint32_t i = blockIdx.x;
-    BatchChunk c;
-    c.n = srcSizes[i];
-    const uint8_t* sp = srcPtrs[i];
-    uint8_t* dp = dstPtrs[i];
-    c.s = gptr(sp);
-    c.d = gptr(dp);
-    c.cap = dstCaps ? dstCaps[i] : c.n + c.n / 255 + 16;   // lz4mtHipCompressBound
-    c.bad = c.n > maxChunk || !dp || (reinterpret_cast<uintptr_t>(dp) & 15) != 0 || (!sp && c.n != 0);
-    return c;
-}
+// runs ends.  The chunk's descriptor and the test for a refused chunk are
+// lz4mt_device.h's BatchChunk / batch_chunk (shared with lz4mt_hc.hip).
 
 // Chunks of any size up to 4 MiB (maxChunk <= 1 << kPosBits, checked by the
 // host): k_encode's LDS layout and per-block choice, 20 KiB and 8 waves per

@@ -6,7 +6,14 @@ kernels on the same bytes at -B4 and -B6 (-Sx, no block checksum) as the
 yardstick: the 64 KiB and 1 MiB batch kernels run the same window code on
 the same blocks.  Prints one JSON line.
 
-    python tools/batch_bench.py [--gib 1] [--reps 10]
+    python tools/batch_bench.py [--gib 1] [--reps 10] [--level L]
+
+--level L times lz4mtHipCompressBatchEx at that level instead (L >= 3:
+LZ4-HC, its workspace of the full lz4mtHipCompressBatchWorkspaceSize unless
+--slots caps it) beside the frame engine's encode time at the same level,
+which is then the chain and parse kernels together, as the batch call's is.
+At 1 MiB the frame engine splits each block's parse over several waves and
+the batch does not: that row is a ratio to record, not a yardstick.
 
 Capacities are the default (d_dstCaps = NULL: the bound of each size), the
 frame encoder's are the block size; every configuration is decoded back and
@@ -44,7 +51,7 @@ def timed(fn, reps, warm=2):
     return statistics.median(ms), min(ms), max(ms)
 
 
-def batch_row(name, src, sizes, reps):
+def batch_row(name, src, sizes, reps, level=0, slots=0):
     n = len(sizes)
     total = int(sizes.sum())
     soff = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
@@ -63,9 +70,19 @@ def batch_row(name, src, sizes, reps):
     max_chunk = int(sizes.max())
     st = P(torch.cuda.current_stream().cuda_stream)
 
+    ws = None
+    if level >= 3:
+        ws = L.batch_compress_workspace(max_chunk, min(n, slots) if slots else n, level)
+    nslots = ws.numel() // L.lib.lz4mtHipCompressBatchWorkspaceSize(max_chunk, 1, level) if level >= 3 else 0
+
     def enc():
-        r = L.lib.lz4mtHipCompressBatch(P(sp.data_ptr()), P(sz.data_ptr()), max_chunk, n, P(cp.data_ptr()), None,
-                                        P(csz.data_ptr()), st)
+        if level == 0:
+            r = L.lib.lz4mtHipCompressBatch(P(sp.data_ptr()), P(sz.data_ptr()), max_chunk, n, P(cp.data_ptr()), None,
+                                            P(csz.data_ptr()), st)
+        else:
+            r = L.lib.lz4mtHipCompressBatchEx(P(sp.data_ptr()), P(sz.data_ptr()), max_chunk, n, P(cp.data_ptr()), None,
+                                              P(csz.data_ptr()), level, P(ws.data_ptr() if level >= 3 else None),
+                                              ws.numel() if level >= 3 else 0, st)
         assert r == 0, r
 
     def dec():
@@ -85,26 +102,30 @@ def batch_row(name, src, sizes, reps):
             assert torch.equal(back[a:a + k], src[b:b + k]), (name, int(i))
     cbytes = int(csz.sum().item())
     gib = total / 2**30
-    return {"name": name, "chunks": n, "bytes": total, "max_chunk": max_chunk,
-            "kernel": "k_encode_batch16" if max_chunk < 65547 else "k_encode_batch", "ratio": round(total / cbytes, 4),
+    kernel = "k_encode_batch16" if max_chunk < 65547 else "k_encode_batch"
+    if level >= 3:
+        kernel = "k_hc_prev_batch + " + ("k_encode_hc_opt_batch" if level >= 10 else "k_encode_hc_batch")
+    hc = {"slots": nslots, "rounds": -(-n // nslots), "workspace_bytes": ws.numel()} if level >= 3 else {}
+    return {"name": name, "chunks": n, "bytes": total, "max_chunk": max_chunk, **hc,
+            "kernel": kernel, "ratio": round(total / cbytes, 4),
             "compress_ms": round(e[0], 3), "compress_ms_min_max": [round(e[1], 3), round(e[2], 3)],
             "compress_gib_s": round(gib / (e[0] / 1e3), 2),
             "decompress_ms": round(d[0], 3), "decompress_ms_min_max": [round(d[1], 3), round(d[2], 3)],
             "decompress_gib_s": round(gib / (d[0] / 1e3), 2)}
 
 
-def frame_row(src, bid, reps):
+def frame_row(src, bid, reps, level=0):
     """the frame engine's encode kernel (timing slot 0 of the compress call) and
     decode kernel (slot 1 of the decompress call), as tools/ktime.py reads them"""
     sd = L.make_sd(bid, False, False)
-    ws = L.compress_workspace(src.numel(), sd)
+    ws = L.compress_workspace(src.numel(), sd, level=level)
     out = torch.empty(L.frame_bound(src.numel(), sd), dtype=torch.uint8, device="cuda")
     dst = torch.empty(src.numel() + (4 << 20), dtype=torch.uint8, device="cuda")
     ms = (ctypes.c_float * 4)()
     L.lib.lz4mtHipSetTiming(1)
     enc, dec = [], []
     for i in range(reps + 2):
-        fr = L.compress_frame(src, sd, out=out, workspace=ws)
+        fr = L.compress_frame(src, sd, out=out, workspace=ws, level=level)
         assert L.lib.lz4mtHipGetTimings(ms) == 0
         e = ms[0]
         got, r = L.decompress_frame(fr, out=dst)
@@ -127,6 +148,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=1.0)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--level", type=int, default=0, help="compression level of the batch and the frame calls")
+    ap.add_argument("--slots", type=int, default=0, help="level >= 3: cap the workspace at this many slots")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("batch_bench.py needs a HIP device")
@@ -134,19 +157,19 @@ def main():
     src = L.gen_synthetic(n, seed=42)
     rows = []
     for name, k in (("4KiB", 4 << 10), ("64KiB", 64 << 10), ("1MiB", 1 << 20)):
-        rows.append(batch_row(name, src, np.full(n // k, k, dtype=np.int64), a.reps))
+        rows.append(batch_row(name, src, np.full(n // k, k, dtype=np.int64), a.reps, a.level, a.slots))
     rs = np.random.RandomState(7)
     sizes = rs.randint(1 << 10, (256 << 10) + 1, size=2 * n // (128 << 10) + 16).astype(np.int64)
     sizes = sizes[:int(np.searchsorted(np.cumsum(sizes), n, side="right"))]
-    rows.append(batch_row("ragged 1KiB-256KiB", src, sizes, a.reps))
-    frames = [frame_row(src, 4, a.reps), frame_row(src, 6, a.reps)]
+    rows.append(batch_row("ragged 1KiB-256KiB", src, sizes, a.reps, a.level, a.slots))
+    frames = [frame_row(src, 4, a.reps, a.level), frame_row(src, 6, a.reps, a.level)]
     by = {r["name"]: r for r in rows}
     gaps = {}
     for nm, fr in (("64KiB", frames[0]), ("1MiB", frames[1])):
         gaps[nm] = {"encode_vs_frame_kernel": round(by[nm]["compress_ms"] / fr["encode_kernel_ms"], 4),
                     "decode_vs_frame_kernel": round(by[nm]["decompress_ms"] / fr["decode_kernel_ms"], 4)}
     print(json.dumps({"tool": "batch_bench", "device": torch.cuda.get_device_name(0), "input": "gen_synthetic seed 42",
-                      "bytes": n, "reps": a.reps, "warmup": 2, "stat": "median", "batch": rows, "frame": frames,
+                      "bytes": n, "level": a.level, "reps": a.reps, "warmup": 2, "stat": "median", "batch": rows, "frame": frames,
                       "batch_over_frame_kernel": gaps}))
 
 
