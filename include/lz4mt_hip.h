@@ -293,6 +293,61 @@ Lz4MtResult lz4mtHipDecompressBatch(const void* const* d_srcPtrs, const uint32_t
                                     void* const* d_dstPtrs, const uint32_t* d_dstCaps, int32_t* d_outSizes,
                                     void* stream);
 
+/* ---- 5b. the batched operators with a shared dictionary -------------------
+ * Small chunks compress badly on their own: each starts with an empty table
+ * and no history.  These calls give every chunk of a batch the same
+ * dictionary, as lz4's LZ4_loadDict + LZ4_compress_fast_continue and
+ * LZ4_decompress_safe_usingDict do.  Everything is device memory; all three
+ * calls are asynchronous, allocate nothing, synchronise nothing and read no
+ * device memory on the host: graph-capturable exactly as the calls above
+ * (including the compress call's read-back probe when captured first).
+ *
+ * State: lz4mtHipDictStateSize() bytes (a constant, a multiple of 256: the
+ * 16 KiB table plus a small header), opaque, 256-byte aligned.
+ * lz4mtHipDictPrepare builds it with one kernel: the table LZ4_loadDict
+ * leaves, and the effective dictionary size.  The dictionary may stand at
+ * any alignment and end on the last byte of its allocation.  The effective
+ * dictionary is the last min(dictSize, LZ4MT_HIP_DICT_WINDOW) bytes, and
+ * none at all when dictSize < 8 (lz4's HASH_UNIT).
+ *
+ * Compress: bytes and d_outSizes[i] are those of, on lz4 1.9.3 and with the
+ * dictionary and the chunk in separate buffers (usingExtDict),
+ *     LZ4_loadDict(stream, dict, dictSize);
+ *     LZ4_compress_fast_continue(stream, src_i, dst_i, size_i, cap_i, 1);
+ * -- 0 when the block does not fit.  Without an effective dictionary that is
+ * still a fresh lz4 *stream* (byU32 table at any size), so chunks below
+ * 65 547 bytes do not get lz4mtHipCompressBatch's byU16 bytes.
+ * d_dstCaps == NULL, maxChunkBytes, the memory contract and the refused
+ * chunks are those of lz4mtHipCompressBatch.  d_dict / dictSize must be what
+ * d_state was prepared for: when the effective size differs from the one
+ * the state records, every chunk gets LZ4MT_HIP_BATCH_BAD_CHUNK and nothing
+ * is written (decided on the device; a guard against a stale state, not a
+ * checksum of the dictionary).
+ *
+ * Decompress: bytes and d_outSizes[i] are those of
+ * LZ4_decompress_safe_usingDict(src, dst, size, cap, dict, dictSize) with the
+ * dictionary not adjacent to dst (every negative return included); with
+ * dictSize == 0 those of lz4mtHipDecompressBatch.  It needs no state, and
+ * the whole dictionary counts (offsets reach its last 65 535 bytes).
+ *
+ * LZ4MT_RESULT_BAD_ARG, in this order: a null array with nChunks > 0
+ * (d_dstCaps may be null for compress only); maxChunkBytes above the
+ * maximum; a null d_dict with dictSize > 0; (prepare, compress) a state
+ * that is null, not 256-byte aligned or smaller than the state size.  Then
+ * LZ4MT_RESULT_ERROR without a HIP device or on a launch error; else
+ * LZ4MT_RESULT_OK (nChunks == 0 launches nothing). */
+#define LZ4MT_HIP_DICT_WINDOW (64u << 10)
+uint64_t lz4mtHipDictStateSize(void);
+Lz4MtResult lz4mtHipDictPrepare(const void* d_dict, uint32_t dictSize, void* d_state, uint64_t stateSize,
+                                void* stream);
+Lz4MtResult lz4mtHipCompressBatchDict(const void* const* d_srcPtrs, const uint32_t* d_srcSizes, uint32_t maxChunkBytes,
+                                      uint32_t nChunks, void* const* d_dstPtrs, const uint32_t* d_dstCaps,
+                                      int32_t* d_outSizes, const void* d_dict, uint32_t dictSize,
+                                      const void* d_state, void* stream);
+Lz4MtResult lz4mtHipDecompressBatchDict(const void* const* d_srcPtrs, const uint32_t* d_srcSizes, uint32_t nChunks,
+                                        void* const* d_dstPtrs, const uint32_t* d_dstCaps, int32_t* d_outSizes,
+                                        const void* d_dict, uint32_t dictSize, void* stream);
+
 /* ---- 6. diagnostics ----------------------------------------------------- */
 /* Runs s_memtime-stamped twins of the encode / decode kernels (never the
  * product launch) and sums per-phase shader cycles over all blocks.

@@ -29,6 +29,7 @@ __all__ = [
     "shard_pack_bound", "shard_reset", "shard_encode", "shard_pack", "shard_unpack", "shard_assemble", "shard_body_bytes",
     "batch_compress_bound", "compress_batch", "decompress_batch", "BATCH_MAX_CHUNK", "BATCH_BAD_CHUNK",
     "batch_compress_workspace", "BATCH_HC_SLOTS",
+    "DICT_WINDOW", "PreparedDict", "prepare_dict", "compress_batch_dict", "decompress_batch_dict",
 ]
 
 lib = _abi.load()
@@ -181,13 +182,15 @@ def batch_compress_workspace(max_chunk, n, level, device=None):
     return torch.empty(nbytes, dtype=torch.uint8, device=device or "cuda")
 
 
-def _batch(fn_name, srcs, caps, null_caps, max_chunk, stream, level=0, workspace=None):
+def _batch(fn_name, srcs, caps, null_caps, max_chunk, stream, level=0, workspace=None, dict_args=None):
     """The common part of compress_batch / decompress_batch: one backing
     allocation for the outputs (each at a 16-byte-aligned offset, ``cap``
     bytes long), the four descriptor arrays built on the host and uploaded
     in one copy, one library call.  Everything is issued on ``stream``.
     ``level`` >= 3 (compress only): lz4mtHipCompressBatchEx, its workspace
-    allocated here on the call's stream unless one is given."""
+    allocated here on the call's stream unless one is given.
+    ``dict_args`` (the dictionary calls): the arguments between d_outSizes
+    and the stream, as ctypes values."""
     n = len(srcs)
     dev = srcs[0].device if n else torch.device("cuda", torch.cuda.current_device())
     if stream is None:
@@ -232,10 +235,10 @@ def _batch(fn_name, srcs, caps, null_caps, max_chunk, stream, level=0, workspace
                                             level, ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), st)
         elif max_chunk is None:
             r = fn(ctypes.c_void_p(d_src), ctypes.c_void_p(d_sz), n, ctypes.c_void_p(d_dst), cap_arg,
-                   ctypes.c_void_p(sizes.data_ptr()), st)
+                   ctypes.c_void_p(sizes.data_ptr()), *(dict_args or ()), st)
         else:
             r = fn(ctypes.c_void_p(d_src), ctypes.c_void_p(d_sz), max_chunk, n, ctypes.c_void_p(d_dst), cap_arg,
-                   ctypes.c_void_p(sizes.data_ptr()), st)
+                   ctypes.c_void_p(sizes.data_ptr()), *(dict_args or ()), st)
         if r != Result.OK:
             raise Lz4MtError(r, fn_name)
         return [back[o:o + c] for o, c in zip(offs, caps)], sizes
@@ -285,6 +288,94 @@ def decompress_batch(blocks, caps, stream=None):
     if len(caps) != len(blocks) or any(c < 0 or c >= 1 << 31 for c in caps):
         raise ValueError("caps: one capacity of 0 .. 2^31 - 1 per block")
     return _batch("lz4mtHipDecompressBatch", blocks, caps, False, None, stream)
+
+
+# the same with a dictionary shared by every chunk (lz4mt_hip.h section 5b)
+DICT_WINDOW = _abi.DICT_WINDOW
+
+
+class PreparedDict:
+    """A dictionary ready for compress_batch_dict: ``dictionary`` (the
+    caller's uint8 device tensor, kept alive here) and ``state`` (the
+    lz4mtHipDictPrepare state, a uint8 device tensor of
+    lz4mtHipDictStateSize bytes)."""
+    __slots__ = ("dictionary", "state")
+
+    def __init__(self, dictionary, state):
+        self.dictionary = dictionary
+        self.state = state
+
+
+def _dict_ptr(dictionary):
+    return ctypes.c_void_p(dictionary.data_ptr() if dictionary.numel() else None), dictionary.numel()
+
+
+def prepare_dict(dictionary, stream=None):
+    """lz4mtHipDictPrepare: builds, with one kernel on ``stream``, the table
+    LZ4_loadDict leaves for ``dictionary`` (a contiguous uint8 device tensor
+    of any size and alignment; its last 64 KiB count, fewer than 8 bytes are
+    no dictionary).  Returns a PreparedDict.  Does not synchronise."""
+    _check_dev(dictionary, "dictionary")
+    if dictionary.numel() >= 1 << 32:
+        raise ValueError("a dictionary is at most 2^32 - 1 bytes")
+    dev = dictionary.device
+    if stream is None:
+        ts = torch.cuda.current_stream(dev)
+    elif isinstance(stream, torch.cuda.Stream):
+        ts = stream
+    else:
+        ts = torch.cuda.ExternalStream(int(stream), device=dev)
+    with torch.cuda.stream(ts):
+        state = torch.empty(int(lib.lz4mtHipDictStateSize()), dtype=torch.uint8, device=dev)
+        dptr, dsize = _dict_ptr(dictionary)
+        r = lib.lz4mtHipDictPrepare(dptr, dsize, ctypes.c_void_p(state.data_ptr()), state.numel(),
+                                    ctypes.c_void_p(ts.cuda_stream))
+    if r != Result.OK:
+        raise Lz4MtError(r, "lz4mtHipDictPrepare")
+    return PreparedDict(dictionary, state)
+
+
+def compress_batch_dict(chunks, prepared, caps=None, stream=None):
+    """lz4mtHipCompressBatchDict: compress_batch (the fast codec) with the
+    dictionary of ``prepared`` (prepare_dict) before every chunk: the bytes of
+    LZ4_loadDict + LZ4_compress_fast_continue.  Returns ``(outs, sizes)`` as
+    compress_batch does; decode with decompress_batch_dict and the same
+    dictionary.  Does not synchronise: ``chunks`` and ``prepared`` must stay
+    alive until ``stream`` has run the call, and ``stream`` must be ordered
+    after the one prepare_dict ran on."""
+    if not isinstance(prepared, PreparedDict):
+        raise TypeError("prepared must come from prepare_dict")
+    chunks = list(chunks)
+    for i, c in enumerate(chunks):
+        _check_dev(c, f"chunks[{i}]")
+    big = max((c.numel() for c in chunks), default=0)
+    if big > BATCH_MAX_CHUNK:
+        raise ValueError(f"a chunk of {big} bytes exceeds the batch maximum of {BATCH_MAX_CHUNK}")
+    dptr, dsize = _dict_ptr(prepared.dictionary)
+    dict_args = (dptr, dsize, ctypes.c_void_p(prepared.state.data_ptr()))
+    if caps is None:
+        return _batch("lz4mtHipCompressBatchDict", chunks, [batch_compress_bound(c.numel()) for c in chunks], True,
+                      big, stream, dict_args=dict_args)
+    caps = [int(c) for c in caps]
+    if len(caps) != len(chunks) or any(c < 0 or c >= 1 << 32 for c in caps):
+        raise ValueError("caps: one capacity of 0 .. 2^32 - 1 per chunk")
+    return _batch("lz4mtHipCompressBatchDict", chunks, caps, False, big, stream, dict_args=dict_args)
+
+
+def decompress_batch_dict(blocks, caps, dictionary, stream=None):
+    """lz4mtHipDecompressBatchDict: decompress_batch against ``dictionary``
+    (a uint8 device tensor, or the PreparedDict the blocks were compressed
+    with): LZ4_decompress_safe_usingDict per block.  Does not synchronise."""
+    if isinstance(dictionary, PreparedDict):
+        dictionary = dictionary.dictionary
+    _check_dev(dictionary, "dictionary")
+    blocks = list(blocks)
+    for i, b in enumerate(blocks):
+        _check_dev(b, f"blocks[{i}]")
+    caps = [int(c) for c in caps]
+    if len(caps) != len(blocks) or any(c < 0 or c >= 1 << 31 for c in caps):
+        raise ValueError("caps: one capacity of 0 .. 2^31 - 1 per block")
+    return _batch("lz4mtHipDecompressBatchDict", blocks, caps, False, None, stream, dict_args=_dict_ptr(dictionary))
 
 
 def frame_bound(n, sd=None):

@@ -35,6 +35,7 @@ Result = type("Result", (), {name: i for i, name in enumerate(RESULT_NAMES)})
 BATCH_MAX_CHUNK = 4 << 20
 BATCH_BAD_CHUNK = -(1 << 31)
 BATCH_HC_SLOTS = 16384
+DICT_WINDOW = 64 << 10
 
 
 class Lz4MtFlg(ctypes.Structure):
@@ -99,6 +100,12 @@ PROTOTYPES = {
     "lz4mtHipCompressBatchEx": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_int,
                                         c_void_p, c_uint64, c_void_p]),
     "lz4mtHipDecompressBatch": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lz4mtHipDictStateSize": (c_uint64, []),
+    "lz4mtHipDictPrepare": (c_int, [c_void_p, c_uint32, c_void_p, c_uint64, c_void_p]),
+    "lz4mtHipCompressBatchDict": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_uint32, c_void_p, c_void_p]),
+    "lz4mtHipDecompressBatchDict": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_uint32, c_void_p]),
     "lz4mtHipFrameBound": (c_uint64, [c_uint64, SD_P]),
     "lz4mtHipCompressWorkspaceSize": (c_uint64, [c_uint64, SD_P]),
     "lz4mtHipCompressFrame": (c_int, [c_void_p, c_uint64, c_void_p, c_uint64, ctypes.POINTER(c_uint64), SD_P,

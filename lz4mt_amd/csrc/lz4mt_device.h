@@ -23,6 +23,17 @@ constexpr int kDecodeOutputTooSmall = INT32_MIN;   // physical slot smaller than
 // per-chunk status of a chunk the kernels refuse (LZ4MT_HIP_BATCH_BAD_CHUNK).
 constexpr uint32_t kBatchMaxChunk = 4u << 20;
 constexpr int32_t kBatchBadChunk = INT32_MIN;
+// The same with a shared dictionary (section 5b): the window LZ4_loadDict
+// keeps, its HASH_UNIT (sizeof(reg_t): a shorter dictionary is none), and the
+// prepared state (the 16 KiB byU32 table + a 256-byte header whose first word
+// is the effective dictionary size).
+constexpr uint32_t kDictWindow = 64u << 10;
+constexpr uint32_t kDictHashUnit = 8;
+constexpr uint32_t kDictStateBytes = 16384 + 256;
+// the compressor's effective dictionary: the last min(dictSize, 64 KiB) bytes, none below HASH_UNIT
+inline uint32_t dict_effective(uint32_t dictSize) {
+    return dictSize < kDictHashUnit ? 0u : (dictSize < kDictWindow ? dictSize : kDictWindow);
+}
 
 #ifdef __HIP__
 // One chunk's descriptor, read at the uniform index blockIdx.x (scalar
@@ -136,6 +147,20 @@ hipError_t launch_encode_batch(const uint8_t* const* srcPtrs, const uint32_t* sr
                                hipStream_t st);
 hipError_t launch_decode_batch(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t nChunks,
                                uint8_t* const* dstPtrs, const uint32_t* dstCaps, int32_t* outSizes, hipStream_t st);
+// the same with a shared dictionary (k_dict_prepare, k_encode_batch_dict,
+// k_decode_batch_dict).  Encode: dictEnd is one past the dictionary's last
+// byte and D = dict_effective(dictSize) bytes before it are the dictionary;
+// state: kDictStateBytes, 256-byte aligned, written by launch_dict_prepare
+// for the same D.  Decode: the whole dictionary counts (dictSize bytes
+// before dictEnd; only the last 65535 can be reached); dictSize > 0.
+hipError_t launch_dict_prepare(const uint8_t* dictEnd, uint32_t D, uint32_t* state, hipStream_t st);
+hipError_t launch_encode_batch_dict(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
+                                    uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps,
+                                    int32_t* outSizes, const uint8_t* dictEnd, uint32_t D, const uint32_t* state,
+                                    hipStream_t st);
+hipError_t launch_decode_batch_dict(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t nChunks,
+                                    uint8_t* const* dstPtrs, const uint32_t* dstCaps, int32_t* outSizes,
+                                    const uint8_t* dictEnd, uint32_t dictSize, hipStream_t st);
 // the serial frame walk fused with the decode (k_decode_walk): records are
 // decoded as the walk publishes them.  ctl: 8 zeroed device words.
 hipError_t launch_decode_walk(const uint8_t* frame, uint64_t frameSize, uint64_t bodyPos, uint32_t blockMax,

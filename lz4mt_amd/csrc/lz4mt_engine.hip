@@ -595,6 +595,63 @@ extern "C" Lz4MtResult lz4mtHipDecompressBatch(const void* const* d_srcPtrs, con
     return LZ4MT_RESULT_OK;
 }
 
+// The batched operators with a shared dictionary (section 5b).  The host
+// only trims the dictionary by pointer arithmetic (its end and its effective
+// size go to the kernels); the state's recorded size is checked on the device.
+static_assert(LZ4MT_HIP_DICT_WINDOW == kDictWindow, "batch ABI");
+extern "C" uint64_t lz4mtHipDictStateSize(void) { return kDictStateBytes; }
+
+static bool dict_state_ok(const void* d_state, uint64_t stateSize) {
+    return d_state && (reinterpret_cast<uintptr_t>(d_state) & 255) == 0 && stateSize >= kDictStateBytes;
+}
+
+extern "C" Lz4MtResult lz4mtHipDictPrepare(const void* d_dict, uint32_t dictSize, void* d_state, uint64_t stateSize,
+                                           void* stream) {
+    if (!d_dict && dictSize > 0) return LZ4MT_RESULT_BAD_ARG;
+    if (!dict_state_ok(d_state, stateSize)) return LZ4MT_RESULT_BAD_ARG;
+    if (!have_device()) return LZ4MT_RESULT_ERROR;
+    HIPCHK(launch_dict_prepare(static_cast<const uint8_t*>(d_dict) + dictSize, dict_effective(dictSize),
+                               static_cast<uint32_t*>(d_state), static_cast<hipStream_t>(stream)));
+    return LZ4MT_RESULT_OK;
+}
+
+extern "C" Lz4MtResult lz4mtHipCompressBatchDict(const void* const* d_srcPtrs, const uint32_t* d_srcSizes,
+                                                 uint32_t maxChunkBytes, uint32_t nChunks, void* const* d_dstPtrs,
+                                                 const uint32_t* d_dstCaps, int32_t* d_outSizes, const void* d_dict,
+                                                 uint32_t dictSize, const void* d_state, void* stream) {
+    if (nChunks && (!d_srcPtrs || !d_srcSizes || !d_dstPtrs || !d_outSizes)) return LZ4MT_RESULT_BAD_ARG;
+    if (maxChunkBytes > LZ4MT_HIP_BATCH_MAX_CHUNK) return LZ4MT_RESULT_BAD_ARG;
+    if (!d_dict && dictSize > 0) return LZ4MT_RESULT_BAD_ARG;
+    if (!dict_state_ok(d_state, kDictStateBytes)) return LZ4MT_RESULT_BAD_ARG;
+    if (!have_device()) return LZ4MT_RESULT_ERROR;
+    if (nChunks == 0) return LZ4MT_RESULT_OK;
+    HIPCHK(launch_encode_batch_dict(reinterpret_cast<const uint8_t* const*>(d_srcPtrs), d_srcSizes, maxChunkBytes,
+                                    nChunks, reinterpret_cast<uint8_t* const*>(d_dstPtrs), d_dstCaps, d_outSizes,
+                                    static_cast<const uint8_t*>(d_dict) + dictSize, dict_effective(dictSize),
+                                    static_cast<const uint32_t*>(d_state), static_cast<hipStream_t>(stream)));
+    return LZ4MT_RESULT_OK;
+}
+
+extern "C" Lz4MtResult lz4mtHipDecompressBatchDict(const void* const* d_srcPtrs, const uint32_t* d_srcSizes,
+                                                   uint32_t nChunks, void* const* d_dstPtrs,
+                                                   const uint32_t* d_dstCaps, int32_t* d_outSizes, const void* d_dict,
+                                                   uint32_t dictSize, void* stream) {
+    if (nChunks && (!d_srcPtrs || !d_srcSizes || !d_dstPtrs || !d_dstCaps || !d_outSizes)) return LZ4MT_RESULT_BAD_ARG;
+    if (!d_dict && dictSize > 0) return LZ4MT_RESULT_BAD_ARG;
+    if (!have_device()) return LZ4MT_RESULT_ERROR;
+    if (nChunks == 0) return LZ4MT_RESULT_OK;
+    if (dictSize == 0)   // LZ4_decompress_safe_usingDict without a dictionary is LZ4_decompress_safe
+        HIPCHK(launch_decode_batch(reinterpret_cast<const uint8_t* const*>(d_srcPtrs), d_srcSizes, nChunks,
+                                   reinterpret_cast<uint8_t* const*>(d_dstPtrs), d_dstCaps, d_outSizes,
+                                   static_cast<hipStream_t>(stream)));
+    else
+        HIPCHK(launch_decode_batch_dict(reinterpret_cast<const uint8_t* const*>(d_srcPtrs), d_srcSizes, nChunks,
+                                        reinterpret_cast<uint8_t* const*>(d_dstPtrs), d_dstCaps, d_outSizes,
+                                        static_cast<const uint8_t*>(d_dict) + dictSize, dictSize,
+                                        static_cast<hipStream_t>(stream)));
+    return LZ4MT_RESULT_OK;
+}
+
 // ===========================================================================
 // 2. device-resident frame engine
 // ===========================================================================

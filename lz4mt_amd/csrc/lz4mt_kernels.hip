@@ -1026,11 +1026,20 @@ struct SimdPrio {
         __builtin_amdgcn_s_setprio(0);
     }
 };
+// XD (XH only; the batched dictionary operator, k_encode_batch_dict): the
+// history is not the block's memory at all -- history position p < o0 is
+// hist[p] (hist = the dictionary's end - o0), and nothing below s + o0 is
+// read through s: the source side never goes below the block (the ring, the
+// catch-up and the literals start at o0 or above), the candidate side goes
+// through xld4 / xld1.  lk.shift is 0: the carried entries' tags are those of
+// the dictionary's bytes (k_dict_prepare).
 template <bool ST, bool U16, bool SPLIT = false, bool LINK = false, bool P17 = false, bool PUB = false,
-          bool XH = false, bool XCHG = true, bool DUP = false>
+          bool XH = false, bool XCHG = true, bool DUP = false, bool XD = false>
 __device__ int32_t encode_block_v5(g_cu8* __restrict__ s, uint32_t n, g_u8* __restrict__ d, uint32_t cap,
                                    l_u32* __restrict__ T, l_u8* __restrict__ R, uint64_t* acc,
-                                   LinkArgs lk = LinkArgs{0, 0, 0, true}, uint32_t* pub = nullptr) {
+                                   LinkArgs lk = LinkArgs{0, 0, 0, true}, uint32_t* pub = nullptr,
+                                   g_cu8* hist = nullptr) {
+    static_assert(!XD || (XH && LINK), "an external history is a LINK / XH variant");
     using G = V5Geo<U16, SPLIT, LINK, P17>;
     const G tab{T};
     const uint32_t L = laneid();
@@ -1040,6 +1049,15 @@ __device__ int32_t encode_block_v5(g_cu8* __restrict__ s, uint32_t n, g_u8* __re
     auto xld4 = [&](uint32_t pos) -> uint32_t {
         if constexpr (!XH) {
             return gld4u(s + pos);
+        } else if constexpr (XD) {
+            if (pos >= o0) return gld4u(s + pos);
+            if (pos + 4 <= o0) return gld4u(hist + pos);
+            uint32_t v = 0;   // straddles the dictionary's end: the rest is the block's start
+            for (uint32_t j = 0; j < 4; ++j) {
+                const uint32_t q = pos + j;
+                v |= (uint32_t)(q < o0 ? hist[q] : s[q]) << (8 * j);
+            }
+            return v;
         } else {
             if (pos >= o0) return gld4u(s + pos);
             if (pos + 4 <= o0) return gld4u(s + pos + lk.shift);
@@ -1053,6 +1071,7 @@ __device__ int32_t encode_block_v5(g_cu8* __restrict__ s, uint32_t n, g_u8* __re
     };
     auto xld1 = [&](uint32_t pos) -> uint32_t {
         if constexpr (!XH) return s[pos];
+        else if constexpr (XD) return pos < o0 ? hist[pos] : s[pos];
         else return s[pos < o0 ? pos + lk.shift : pos];
     };
     const uint32_t blen = n - o0;
@@ -1593,6 +1612,94 @@ __global__ void __launch_bounds__(64) k_encode_batch16(const uint8_t* const* __r
     if (laneid() == 0) outSizes[blockIdx.x] = r;
 }
 
+// ---- the batched operators with a shared dictionary (lz4mt_hip.h section
+// 5b): every chunk is LZ4_loadDict(dict) + LZ4_compress_fast_continue(chunk)
+// of lz4 1.9.3 with the dictionary in a buffer of its own (usingExtDict).
+// In the LINK coordinates that is: the chunk at kLinkO0 (loadDict leaves
+// currentOffset = 64 KiB), the effective dictionary (its last D <= 64 KiB
+// bytes, D = 0 below 8 bytes) at [kLinkO0 - D, kLinkO0).
+//
+// The state (kDictStateBytes, 256-byte aligned): words [0, 4096) the byU32
+// table as loadDict leaves it, in the LINK encoder's entry format (position
+// | tag << 23); word 4096 the effective dictionary size D it was built for;
+// the rest zero.
+static_assert(kDictStateBytes % 16 == 0 && kDictStateBytes / 4 > 4096 && kDictWindow == kLinkO0, "dictionary state");
+
+// loadDict's table: positions p = kLinkO0 - D, + 3, + 6, ... <= kLinkO0 - 8
+// are inserted in ascending order (hash5 of the 8 bytes at p, 12 bits), a
+// later one replacing an earlier one: an entry is the LARGEST inserted
+// position of its bucket, so an atomic max over (position << 9 | tag) builds
+// it in any order (the position decides; the tag is that position's own).
+// Buckets nothing was inserted into stay 0.  One workgroup: at most 21 846
+// positions, the table in LDS.  dictEnd: one past the dictionary's last byte;
+// it is read by bytes (any alignment, nothing outside [dictEnd - D, dictEnd)).
+__global__ void __launch_bounds__(1024) k_dict_prepare(const uint8_t* __restrict__ dictEnd, uint32_t D,
+                                                       uint32_t* __restrict__ state) {
+    using G = V5Geo<false, false, true>;
+    static_assert(G::PB + G::TB == 32 && G::TB == 9, "the packed (position, tag) fits a word");
+    __shared__ uint32_t Tp[4096];
+    const uint32_t t = threadIdx.x;
+    for (uint32_t i = t; i < 4096; i += 1024) Tp[i] = 0;
+    __syncthreads();
+    g_cu8* h = gptr(dictEnd) - kLinkO0;   // h[p]: the byte at position p, valid for p in [kLinkO0 - D, kLinkO0)
+    const uint32_t lo = kLinkO0 - D;
+    if (D >= kDictHashUnit) {
+        const uint32_t cnt = (D - kDictHashUnit) / 3 + 1;
+        for (uint32_t k = t; k < cnt; k += 1024) {
+            const uint32_t p = lo + 3 * k;
+            uint32_t w0 = 0, b4 = h[p + 4];
+            for (uint32_t j = 0; j < 4; ++j) w0 |= (uint32_t)h[p + j] << (8 * j);
+            const uint32_t hs = lz4_hash<false>(w0, b4);   // (hash5 takes the low 5 bytes)
+            atomicMax(&Tp[hs], (p << G::TB) | G::tag(w0));
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = t; i < kDictStateBytes / 4; i += 1024) {
+        uint32_t v = 0;
+        if (i < 4096) {
+            const uint32_t e = Tp[i];
+            v = (e >> G::TB) | (e << G::PB);
+        } else if (i == 4096) {
+            v = D;
+        }
+        state[i] = v;
+    }
+}
+
+// One wave per chunk, k_encode_batch's conventions (no wait on another wave,
+// no loop over chunks, no atomics).  The 16 KiB table comes from the state
+// into LDS (read-only, shared by every wave: it stays in L2); the LINK / XH /
+// XD encoder then runs one stream step: catch-up bound kLinkO0 for a
+// candidate in the chunk, kLinkO0 - D for one in the dictionary, candidates
+// below kLinkO0 - D refused (dictSmall; with D = 64 KiB the bound is 0 and
+// the distance test alone decides, noDictIssue).  k_encode's LDS layout, 20
+// KiB and 8 waves per CU.  A state built for another dictionary size refuses
+// every chunk.
+template <bool XC>
+__global__ void __launch_bounds__(64) k_encode_batch_dict(const uint8_t* const* __restrict__ srcPtrs,
+                                                          const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
+                                                          uint8_t* const* __restrict__ dstPtrs,
+                                                          const uint32_t* __restrict__ dstCaps,
+                                                          int32_t* __restrict__ outSizes,
+                                                          const uint8_t* __restrict__ dictEnd, uint32_t D,
+                                                          const uint32_t* __restrict__ state) {
+    ENCODE_LDS
+    (void)S;
+    const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, dstCaps);
+    const uint32_t L = laneid();
+    int32_t r = kBatchBadChunk;
+    if (!c.bad && state[4096] == D) {
+        g_cu4* in = (g_cu4*)state;
+        for (uint32_t i = L; i < 1024; i += 64) ((l_u4*)T)[i] = in[i];
+        WAVE_SYNC();
+        const LinkArgs lk{kLinkO0, kLinkO0 - D, kLinkO0 - D, false};
+        r = encode_block_v5<false, false, false, true, false, false, true, XC, false, true>(
+            c.s - kLinkO0, kLinkO0 + c.n, c.d, c.cap, (l_u32*)T, (l_u8*)X, nullptr, lk, nullptr,
+            gptr(dictEnd) - kLinkO0);
+    }
+    if (L == 0) outSizes[blockIdx.x] = r;
+}
+
 // A block-dependent table entry (position | tag, V5Geo<false, false, true>)
 // in the next block's coordinates: position x -> x - n; positions at or
 // below n (older than the next block's 64 KiB window) -> 0, stale like an
@@ -2070,6 +2177,30 @@ hipError_t launch_encode_batch(const uint8_t* const* srcPtrs, const uint32_t* sr
     }
     return hipSuccess;
 }
+
+// The dictionary operators.  dictEnd / D: the effective dictionary
+// (dict_effective); state: kDictStateBytes, 256-byte aligned.
+hipError_t launch_dict_prepare(const uint8_t* dictEnd, uint32_t D, uint32_t* state, hipStream_t st) {
+    hipLaunchKernelGGL(k_dict_prepare, dim3(1), dim3(1024), 0, st, dictEnd, D, state);
+    return hipGetLastError();
+}
+
+hipError_t launch_encode_batch_dict(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
+                                    uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps,
+                                    int32_t* outSizes, const uint8_t* dictEnd, uint32_t D, const uint32_t* state,
+                                    hipStream_t st) {
+    bool xc = true;
+    if (const hipError_t r = encoder_path(st, &xc); r != hipSuccess) return r;
+    const auto k = xc ? k_encode_batch_dict<true> : k_encode_batch_dict<false>;
+    for (uint32_t o = 0; o < nChunks;) {
+        const uint32_t g = std::min(nChunks - o, kBatchGrid);
+        hipLaunchKernelGGL(k, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, maxChunk, dstPtrs + o,
+                           dstCaps ? dstCaps + o : nullptr, outSizes + o, dictEnd, D, state);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        o += g;
+    }
+    return hipSuccess;
+}
 #endif
 
 
@@ -2128,8 +2259,19 @@ static_assert(kRing + kWinAlloc <= 20480 || kRing != 16384, "decoder LDS: 8 wave
 // HG: no dword that lies wholly before src is read either (the batched
 // block kernel: nothing of the caller's precedes a chunk).  A frame's block
 // has the frame before it, so the window's first 16 bytes load whole.
-template <bool ST, bool HG = false>
-struct Dec {
+// XD (the batched operator with a dictionary, k_decode_batch_dict): output
+// positions below 0 are the bytes of an external dictionary, hist[-1] its
+// last one (lz4's usingExtDict) -- not memory before dst.  lowP = -(its
+// size) bounds the offsets as for a prefix; every path that reads output no
+// longer in the ring (out8) takes such a byte from hist, and a match that
+// runs from the dictionary into the block goes by the serial copy, whose
+// per-byte sources follow the virtual history (dictionary, then output).
+template <bool XD> struct DecHist {};
+template <> struct DecHist<true> {
+    g_cu8* hist;          // one past the dictionary's last byte
+};
+template <bool ST, bool HG = false, bool XD = false>
+struct Dec : DecHist<XD> {
     uint64_t* acc;
     uint64_t ts;
     g_cu8* src;           // compressed block
@@ -2144,6 +2286,14 @@ struct Dec {
     int64_t flushed;      // [0, flushed) stored to dst
     int64_t completed;    // [0, completed) known complete in memory
     int32_t lowP;         // lowest position a match may read: 0, or -65536 with a 64 KiB prefix before dst
+    // an output byte from memory (one the ring no longer holds, or a prefix
+    // byte); XD: below 0 the dictionary's
+    __device__ __forceinline__ uint32_t out8(int64_t sp) const {
+        if constexpr (XD) {
+            if (sp < 0) return this->hist[sp];
+        }
+        return dst[sp];
+    }
     __device__ __forceinline__ void refill(int64_t i) {
         const uintptr_t base = (reinterpret_cast<uintptr_t>(src) + (uintptr_t)i) & ~uintptr_t(15);
         wlo = (int64_t)(base - reinterpret_cast<uintptr_t>(src));
@@ -2245,7 +2395,7 @@ struct Dec {
                         const uint32_t kq = (L * magic) >> 16;   // L / offset for L < 64
                         sp = o + L - (int64_t)(kq + 1) * offset;
                     }
-                    v = (sp >= o - kRing && sp >= 0) ? ring[sp & (kRing - 1)] : dst[sp];
+                    v = (sp >= o - kRing && sp >= 0) ? ring[sp & (kRing - 1)] : out8(sp);
                 }
                 ring[(o + L) & (kRing - 1)] = (uint8_t)v;
             }
@@ -2437,8 +2587,8 @@ struct Dec {
                     flane[g] = lg;
                     const int64_t fs = (int32_t)rdlane((uint32_t)src, (int)lg);   // a prefix source is negative
                     const uint32_t fz = rdlane(mlen, (int)lg);
-                    fv[g] = dst[fs + min(L, fz - 1)];   // bytes past the match repeat its last one (never written)
-                    if (fz > 64) fv2[g] = dst[fs + min(L + 64, fz - 1)];
+                    fv[g] = out8(fs + min(L, fz - 1));   // bytes past the match repeat its last one (never written)
+                    if (fz > 64) fv2[g] = out8(fs + min(L + 64, fz - 1));
                 }
             }
         }
@@ -2556,8 +2706,8 @@ struct Dec {
                 const uint32_t js = (uint32_t)rdlane((uint32_t)src, j), jm = rdlane(mlen, j);
                 const uint32_t jo = (uint32_t)rdlane((uint32_t)om, j);
                 const int64_t jsS = (int32_t)js;
-                const uint32_t a0 = L < jm ? (uint32_t)dst[jsS + L] : 0u;
-                const uint32_t a1 = L + 64 < jm ? (uint32_t)dst[jsS + 64 + L] : 0u;
+                const uint32_t a0 = L < jm ? out8(jsS + L) : 0u;
+                const uint32_t a1 = L + 64 < jm ? out8(jsS + 64 + L) : 0u;
                 if (L < jm) ring[(jo + L) & (kRing - 1)] = (uint8_t)a0;
                 if (L + 64 < jm) ring[(jo + 64 + L) & (kRing - 1)] = (uint8_t)a1;
                 farLeft &= farLeft - 1;
@@ -2614,8 +2764,12 @@ struct Dec {
 
 // LZ4_decompress_safe (lz4 1.9.3, LZ4_FAST_DEC_LOOP=1): same accept/reject
 // decisions and return values as the oracle restatement (oracle/lz4_oracle.c).
-template <bool ST, bool HG>
-__device__ int32_t decode_block(Dec<ST, HG>& D, int64_t cap) {
+// XD: LZ4_decompress_safe_usingDict with the dictionary away from dst
+// (forceExtDict): lz4 takes its short match copies only for a match inside
+// the block (match >= lowPrefix), so a match that starts in the dictionary
+// always passes the end-of-output test of the safe match copy.
+template <bool ST, bool HG, bool XD>
+__device__ int32_t decode_block(Dec<ST, HG, XD>& D, int64_t cap) {
     const int64_t iend = D.len, oend = cap;
     const int64_t shortiend = iend - 16, shortoend = oend - 32;
     int64_t ip = 0, op = 0, cpy = 0, match = 0, length = 0, ext = 0;
@@ -2684,7 +2838,7 @@ __device__ int32_t decode_block(Dec<ST, HG>& D, int64_t cap) {
         } else {
             length += kMinMatch;
             if (op + length >= oend - 64) goto safe_match_copy;
-            if (match >= D.lowP && offset >= 8) {
+            if (match >= (XD ? 0 : D.lowP) && offset >= 8) {
                 PHYS_CHECK(op + length);
                 D.copy_seq(plIp, plOp, plLen, offset, length);
                 op += length;
@@ -2711,7 +2865,7 @@ safe_decode:
             offset = D.in8(ip) | (D.in8(ip + 1) << 8);
             ip += 2;
             match = op - (int64_t)offset;
-            if (length != 15 && offset >= 8 && match >= D.lowP) {
+            if (length != 15 && offset >= 8 && match >= (XD ? 0 : D.lowP)) {
                 PHYS_CHECK(op + length + kMinMatch);
                 D.copy_seq(plIp, plOp, plLen, offset, length + kMinMatch);
                 op += length + kMinMatch;
@@ -2879,6 +3033,51 @@ __global__ void __launch_bounds__(64) k_decode_batch(const uint8_t* const* __res
         D.lowP = 0;
         res = decode_block(D, (int64_t)cap);
         if (res == kDecodeOutputTooSmall) res = -1;   // (unreachable with physcap = cap; mapped as the block operator maps it)
+    }
+    if (laneid() == 0) outSizes[i] = res;
+}
+
+// The same against a shared dictionary of dictSize > 0 bytes that ends at
+// dictEnd (any alignment; only [dictEnd - dictSize, dictEnd) is read):
+// LZ4_decompress_safe_usingDict with the dictionary away from dst.  An
+// offset is refused only below dst - dictSize, and only when dictSize < 64
+// KiB (an offset reaches 65535 at most).  k_decode_batch's LDS, 8 waves per CU.
+__global__ void __launch_bounds__(64) k_decode_batch_dict(const uint8_t* const* __restrict__ srcPtrs,
+                                                          const uint32_t* __restrict__ srcSizes,
+                                                          uint8_t* const* __restrict__ dstPtrs,
+                                                          const uint32_t* __restrict__ dstCaps,
+                                                          int32_t* __restrict__ outSizes,
+                                                          const uint8_t* __restrict__ dictEnd, uint32_t dictSize) {
+    __shared__ __attribute__((aligned(16))) uint8_t ring[kRing];
+    __shared__ __attribute__((aligned(16))) uint8_t win[kWinAlloc];
+    const uint32_t i = blockIdx.x;
+    const uint32_t len = srcSizes[i], cap = dstCaps[i];
+    const uint8_t* sp = srcPtrs[i];
+    uint8_t* dp = dstPtrs[i];
+    int32_t res;
+    if (!dp || (reinterpret_cast<uintptr_t>(dp) & 15) != 0 || (!sp && len != 0)) {
+        res = kBatchBadChunk;
+    } else if (len > 0x7FFFFFFFu || cap > 0x7FFFFFFFu) {
+        res = -1;
+    } else {
+        Dec<false, true, true> D;
+        D.hist = gptr(dictEnd);
+        D.acc = nullptr;
+        D.ts = 0;
+        D.src = gptr(sp);
+        D.len = (int64_t)len;
+        D.dst = gptr(dp);
+        D.physcap = (int64_t)cap;
+        D.ring = (l_u8*)ring;
+        D.win = (l_u8*)win;
+        D.wlo = INT64_MIN / 4;
+        D.labase = INT64_MIN / 4;
+        D.la = 0;
+        D.flushed = 0;
+        D.completed = 0;
+        D.lowP = -(int32_t)min(dictSize, 65536u);
+        res = decode_block(D, (int64_t)cap);
+        if (res == kDecodeOutputTooSmall) res = -1;
     }
     if (laneid() == 0) outSizes[i] = res;
 }
@@ -3474,6 +3673,20 @@ hipError_t launch_decode_batch(const uint8_t* const* srcPtrs, const uint32_t* sr
         const uint32_t g = std::min(nChunks - o, kGrid);
         hipLaunchKernelGGL(k_decode_batch, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, dstPtrs + o,
                            dstCaps + o, outSizes + o);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        o += g;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_decode_batch_dict(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t nChunks,
+                                    uint8_t* const* dstPtrs, const uint32_t* dstCaps, int32_t* outSizes,
+                                    const uint8_t* dictEnd, uint32_t dictSize, hipStream_t st) {
+    constexpr uint32_t kGrid = 1u << 30;
+    for (uint32_t o = 0; o < nChunks;) {
+        const uint32_t g = std::min(nChunks - o, kGrid);
+        hipLaunchKernelGGL(k_decode_batch_dict, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, dstPtrs + o,
+                           dstCaps + o, outSizes + o, dictEnd, dictSize);
         if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
         o += g;
     }

@@ -6,7 +6,7 @@ kernels on the same bytes at -B4 and -B6 (-Sx, no block checksum) as the
 yardstick: the 64 KiB and 1 MiB batch kernels run the same window code on
 the same blocks.  Prints one JSON line.
 
-    python tools/batch_bench.py [--gib 1] [--reps 10] [--level L]
+    python tools/batch_bench.py [--gib 1] [--reps 10] [--level L] [--dict-kib K]
 
 --level L times lz4mtHipCompressBatchEx at that level instead (L >= 3:
 LZ4-HC, its workspace of the full lz4mtHipCompressBatchWorkspaceSize unless
@@ -14,6 +14,13 @@ LZ4-HC, its workspace of the full lz4mtHipCompressBatchWorkspaceSize unless
 which is then the chain and parse kernels together, as the batch call's is.
 At 1 MiB the frame engine splits each block's parse over several waves and
 the batch does not: that row is a ratio to record, not a yardstick.
+
+--dict-kib K times the dictionary calls (lz4mtHipCompressBatchDict /
+lz4mtHipDecompressBatchDict; lz4mtHipDictPrepare on its own) with a
+dictionary of K KiB, the last K KiB of the same App. F input in a tensor of
+its own.  The yardstick is then the plain batch call on the same chunks in
+the same run: every row carries both times, both compression ratios and
+their quotients, and the frame rows are left out.
 
 Capacities are the default (d_dstCaps = NULL: the bound of each size), the
 frame encoder's are the block size; every configuration is decoded back and
@@ -51,7 +58,7 @@ def timed(fn, reps, warm=2):
     return statistics.median(ms), min(ms), max(ms)
 
 
-def batch_row(name, src, sizes, reps, level=0, slots=0):
+def batch_row(name, src, sizes, reps, level=0, slots=0, dct=None):
     n = len(sizes)
     total = int(sizes.sum())
     soff = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
@@ -90,18 +97,52 @@ def batch_row(name, src, sizes, reps, level=0, slots=0):
                                           P(dsz.data_ptr()), st)
         assert r == 0, r
 
+    def round_trip():   # once per codec: sizes and bytes
+        assert bool((csz > 0).all()) and torch.equal(dsz, sz), name
+        if bool(np.all(boff[1:] - boff[:-1] == sizes[:-1])):   # outputs contiguous: one compare
+            assert torch.equal(back[:total], src[:total]), name
+        else:
+            for i in np.random.RandomState(1).choice(n, size=min(n, 2000), replace=False):
+                a, b, k = int(boff[i]), int(soff[i]), int(sizes[i])
+                assert torch.equal(back[a:a + k], src[b:b + k]), (name, int(i))
+
     e = timed(enc, reps)
     d = timed(dec, reps)
-    # round trip, once: sizes and bytes
-    assert bool((csz > 0).all()) and torch.equal(dsz, sz), name
-    if bool(np.all(boff[1:] - boff[:-1] == sizes[:-1])):   # outputs contiguous: one compare
-        assert torch.equal(back[:total], src[:total]), name
-    else:
-        for i in np.random.RandomState(1).choice(n, size=min(n, 2000), replace=False):
-            a, b, k = int(boff[i]), int(soff[i]), int(sizes[i])
-            assert torch.equal(back[a:a + k], src[b:b + k]), (name, int(i))
+    round_trip()
     cbytes = int(csz.sum().item())
     gib = total / 2**30
+    if dct is not None:
+        dictionary, state = dct
+
+        def enc_d():
+            r = L.lib.lz4mtHipCompressBatchDict(P(sp.data_ptr()), P(sz.data_ptr()), max_chunk, n, P(cp.data_ptr()),
+                                                None, P(csz.data_ptr()), P(dictionary.data_ptr()), dictionary.numel(),
+                                                P(state.data_ptr()), st)
+            assert r == 0, r
+
+        def dec_d():
+            r = L.lib.lz4mtHipDecompressBatchDict(P(cp.data_ptr()), P(csz.data_ptr()), n, P(bp.data_ptr()),
+                                                  P(sz.data_ptr()), P(dsz.data_ptr()), P(dictionary.data_ptr()),
+                                                  dictionary.numel(), st)
+            assert r == 0, r
+
+        back.zero_()
+        ed = timed(enc_d, reps)
+        dd = timed(dec_d, reps)
+        round_trip()
+        dbytes = int(csz.sum().item())
+        return {"name": name, "chunks": n, "bytes": total, "max_chunk": max_chunk,
+                "kernel": "k_encode_batch_dict / k_decode_batch_dict",
+                "plain_kernel": "k_encode_batch16" if max_chunk < 65547 else "k_encode_batch",
+                "ratio": round(total / dbytes, 4), "plain_ratio": round(total / cbytes, 4),
+                "compress_ms": round(ed[0], 3), "compress_ms_min_max": [round(ed[1], 3), round(ed[2], 3)],
+                "compress_gib_s": round(gib / (ed[0] / 1e3), 2),
+                "decompress_ms": round(dd[0], 3), "decompress_ms_min_max": [round(dd[1], 3), round(dd[2], 3)],
+                "decompress_gib_s": round(gib / (dd[0] / 1e3), 2),
+                "plain_compress_ms": round(e[0], 3), "plain_compress_ms_min_max": [round(e[1], 3), round(e[2], 3)],
+                "plain_decompress_ms": round(d[0], 3),
+                "plain_decompress_ms_min_max": [round(d[1], 3), round(d[2], 3)],
+                "compress_over_plain": round(ed[0] / e[0], 4), "decompress_over_plain": round(dd[0] / d[0], 4)}
     kernel = "k_encode_batch16" if max_chunk < 65547 else "k_encode_batch"
     if level >= 3:
         kernel = "k_hc_prev_batch + " + ("k_encode_hc_opt_batch" if level >= 10 else "k_encode_hc_batch")
@@ -150,18 +191,41 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--level", type=int, default=0, help="compression level of the batch and the frame calls")
     ap.add_argument("--slots", type=int, default=0, help="level >= 3: cap the workspace at this many slots")
+    ap.add_argument("--dict-kib", type=int, default=0, help="time the dictionary calls with a dictionary of K KiB")
     a = ap.parse_args()
+    if a.dict_kib and a.level >= 3:
+        sys.exit("--dict-kib times the fast codec: no --level")
     if not torch.cuda.is_available():
         sys.exit("batch_bench.py needs a HIP device")
     n = int(a.gib * 2**30) & ~((1 << 20) - 1)
     src = L.gen_synthetic(n, seed=42)
+    dct, prep = None, {}
+    if a.dict_kib:
+        dictionary = src[n - (a.dict_kib << 10):].clone()
+        state = torch.empty(L.lib.lz4mtHipDictStateSize(), dtype=torch.uint8, device="cuda")
+        st = P(torch.cuda.current_stream().cuda_stream)
+
+        def prepare():
+            r = L.lib.lz4mtHipDictPrepare(P(dictionary.data_ptr()), dictionary.numel(), P(state.data_ptr()),
+                                          state.numel(), st)
+            assert r == 0, r
+
+        pm = timed(prepare, a.reps)
+        dct = (dictionary, state)
+        prep = {"dict_bytes": dictionary.numel(), "dict": "the input's last bytes", "state_bytes": state.numel(),
+                "prepare_ms": round(pm[0], 4), "prepare_ms_min_max": [round(pm[1], 4), round(pm[2], 4)]}
     rows = []
     for name, k in (("4KiB", 4 << 10), ("64KiB", 64 << 10), ("1MiB", 1 << 20)):
-        rows.append(batch_row(name, src, np.full(n // k, k, dtype=np.int64), a.reps, a.level, a.slots))
+        rows.append(batch_row(name, src, np.full(n // k, k, dtype=np.int64), a.reps, a.level, a.slots, dct))
     rs = np.random.RandomState(7)
     sizes = rs.randint(1 << 10, (256 << 10) + 1, size=2 * n // (128 << 10) + 16).astype(np.int64)
     sizes = sizes[:int(np.searchsorted(np.cumsum(sizes), n, side="right"))]
-    rows.append(batch_row("ragged 1KiB-256KiB", src, sizes, a.reps, a.level, a.slots))
+    rows.append(batch_row("ragged 1KiB-256KiB", src, sizes, a.reps, a.level, a.slots, dct))
+    if dct is not None:   # the yardstick is the plain batch call, in every row
+        print(json.dumps({"tool": "batch_bench", "device": torch.cuda.get_device_name(0),
+                          "input": "gen_synthetic seed 42", "bytes": n, "level": 0, "reps": a.reps, "warmup": 2,
+                          "stat": "median", **prep, "batch": rows}))
+        return
     frames = [frame_row(src, 4, a.reps, a.level), frame_row(src, 6, a.reps, a.level)]
     by = {r["name"]: r for r in rows}
     gaps = {}
