@@ -28,8 +28,17 @@ def build():
     subprocess.run(["make", "-C", HERE, "-s"], check=True)
 
 
-def _load():
+def _stale():
+    """The library is missing, or older than one of the sources it is made of."""
     if not os.path.exists(LIB_PATH):
+        return True
+    built = os.path.getmtime(LIB_PATH)
+    return any(f.endswith((".c", ".h")) and os.path.getmtime(os.path.join(HERE, f)) > built
+               for f in os.listdir(HERE))
+
+
+def _load():
+    if _stale():
         build()
     lib = ctypes.CDLL(LIB_PATH)
     u8p, sz = ctypes.c_void_p, ctypes.c_size_t
@@ -40,6 +49,8 @@ def _load():
     lib.orc_lz4_decompress_safe.argtypes = [u8p, u8p, ctypes.c_int, ctypes.c_int]
     lib.orc_lz4hc_compress.argtypes = [u8p, u8p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lib.orc_lz4_decompress_safe_prefix64k.argtypes = [u8p, u8p, ctypes.c_int, ctypes.c_int]
+    lib.orc_lz4_compress_dict.argtypes = [u8p, ctypes.c_int, u8p, u8p, ctypes.c_int, ctypes.c_int]
+    lib.orc_lz4_decompress_safe_usingDict.argtypes = [u8p, u8p, ctypes.c_int, ctypes.c_int, u8p, ctypes.c_int]
     lib.orc_frame_bound.restype = sz
     lib.orc_frame_bound.argtypes = [sz, ctypes.POINTER(FrameParams)]
     lib.orc_frame_compress.restype = sz
@@ -118,6 +129,23 @@ def decompress_block_prefix64k(block, cap, prefix=b""):
     buf = ctypes.create_string_buffer(hist + bytes(max(cap, 1) + 16), 65536 + max(cap, 1) + 16)
     n = lib.orc_lz4_decompress_safe_prefix64k(_buf(block), ctypes.byref(buf, 65536), len(block), cap)
     return n, (buf.raw[65536:65536 + n] if n > 0 else b"")
+
+
+def compress_block_dict(d, data, cap=None):
+    """LZ4_loadDict(d) on a fresh stream + LZ4_compress_fast_continue(data, cap, 1) restated, the
+    dictionary in a buffer of its own; b'' when it does not fit.  ``cap`` defaults to the bound."""
+    cap = lib.orc_lz4_compress_bound(len(data)) if cap is None else cap
+    dst = ctypes.create_string_buffer(max(cap, lib.orc_lz4_compress_bound(len(data))) + 16)
+    n = lib.orc_lz4_compress_dict(_buf(d), len(d), _buf(data), dst, len(data), cap)
+    return dst.raw[:n]
+
+
+def decompress_block_dict(block, cap, d):
+    """LZ4_decompress_safe_usingDict restated (the whole of ``d`` is the dictionary, away from the
+    destination): (ret, bytes)."""
+    dst = ctypes.create_string_buffer(max(cap, 1) + 16)
+    n = lib.orc_lz4_decompress_safe_usingDict(_buf(block), dst, len(block), cap, _buf(d), len(d))
+    return n, (dst.raw[:n] if n > 0 else b"")
 
 
 def params(block_max_id=7, stream_checksum=True, block_checksum=False, stream_size=None):

@@ -233,6 +233,160 @@ fail:
 }
 
 /* ===================================================================== */
+/* LZ4 1.9.3 LZ4_loadDict on a fresh stream, then one                     */
+/* LZ4_compress_fast_continue(.., acceleration 1) with the dictionary and */
+/* the source in buffers of their own (DESIGN.md 4.9 "With a dictionary").*/
+/* Positions are stream indices: loadDict leaves currentOffset = 64 KiB,  */
+/* so the source is [O, O + n) and the effective dictionary (the last 64  */
+/* KiB; none below HASH_UNIT = 8 bytes) is [O - D, O).  The parse is      */
+/* byU32 (hash5, 12 bits) at every size, usingExtDict, limitedOutput at   */
+/* every capacity; dictSmall below 64 KiB (a candidate below O - D is     */
+/* refused; without a dictionary that is every entry of the all-zero      */
+/* table), noDictIssue at 64 KiB (O - D = 0: only the distance test).     */
+/* ===================================================================== */
+#define DICT_O 65536u
+#define HASH_UNIT 8
+
+int orc_lz4_compress_dict(const uint8_t* dict, int dictSize, const uint8_t* src, uint8_t* dst, int n, int cap) {
+    if ((unsigned)n > (unsigned)MAX_INPUT) return 0;
+    if (n == 0) {
+        if (cap <= 0) return 0;
+        dst[0] = 0;
+        return 1;
+    }
+    const uint32_t O = DICT_O;
+    const uint32_t D = (dict == NULL || dictSize < HASH_UNIT) ? 0 : (dictSize > (int)O ? O : (uint32_t)dictSize);
+    const uint8_t* const dictEnd = D ? dict + dictSize : NULL;
+    /* the byte at stream position p: dictionary below O, source from O up */
+#define AT(p) ((p) >= O ? src + ((p) - O) : dictEnd - (O - (p)))
+    const uint32_t low = O - D;                    /* dictionary start = dictSmall's limit */
+    uint32_t* T = (uint32_t*)calloc(4096, sizeof(uint32_t));
+    /* loadDict: every third position that has 8 bytes left, later over earlier */
+    for (uint32_t p = low; D && p + HASH_UNIT <= O; p += 3) T[hpos(AT(p), 0)] = p;
+
+    const uint32_t end = O + (uint32_t)n;
+    const uint32_t mflimitP1 = end - MFLIMIT + 1;
+    const uint32_t matchlimit = end - LASTLITERALS;
+    uint32_t anchor = O, ip = O, cand = 0, fh, token;
+    size_t op = 0;
+    int result = 0;
+
+    if (n < MIN_LENGTH) goto last_literals;
+    T[hpos(src, 0)] = O;
+    ip = O + 1;
+    fh = hpos(AT(ip), 0);
+
+    for (;;) {
+        {
+            uint32_t fip = ip, step = 1, nb = 64;
+            for (;;) {
+                const uint32_t h = fh, cur = fip;
+                cand = T[h];
+                ip = fip;
+                fip += step;
+                step = nb++ >> 6;
+                if (fip > mflimitP1) goto last_literals;
+                fh = hpos(AT(fip), 0);
+                T[h] = cur;
+                if (cand < low) continue;              /* dictSmall: outside the valid area */
+                if (cand + DIST_MAX < cur) continue;   /* too far */
+                if (rd32(AT(cand)) == rd32(AT(ip))) break;
+            }
+        }
+        /* Catch up: down to the dictionary's first byte for a candidate in
+         * the dictionary, to the source's first byte for one in the source. */
+        {
+            const uint32_t lowLimit = cand < O ? low : O;
+            while (ip > anchor && cand > lowLimit && *AT(ip - 1) == *AT(cand - 1)) { ip--; cand--; }
+        }
+        {
+            const uint32_t lit = ip - anchor;
+            token = (uint32_t)op++;
+            if (op + lit + 8 + lit / 255 > (size_t)cap) goto fail;
+            if (lit >= 15) {
+                uint32_t len = lit - 15;
+                dst[token] = 15 << 4;
+                for (; len >= 255; len -= 255) dst[op++] = 255;
+                dst[op++] = (uint8_t)len;
+            } else {
+                dst[token] = (uint8_t)(lit << 4);
+            }
+            memcpy(dst + op, AT(anchor), lit);
+            op += lit;
+        }
+    next_match:
+        {
+            const uint32_t off = ip - cand;
+            dst[op++] = (uint8_t)off;
+            dst[op++] = (uint8_t)(off >> 8);
+            uint32_t mc = 0;
+            if (cand < O) {
+                /* a match in the dictionary ends at the dictionary's end and
+                 * then goes on against the source's first bytes */
+                uint32_t limit = ip + (O - cand);
+                if (limit > matchlimit) limit = matchlimit;
+                while (ip + MINMATCH + mc < limit && *AT(ip + MINMATCH + mc) == *AT(cand + MINMATCH + mc)) mc++;
+                ip += mc + MINMATCH;
+                if (ip == limit) {
+                    uint32_t more = 0;
+                    while (ip + more < matchlimit && *AT(ip + more) == src[more]) more++;
+                    mc += more;
+                    ip += more;
+                }
+            } else {
+                while (ip + MINMATCH + mc < matchlimit && *AT(ip + MINMATCH + mc) == *AT(cand + MINMATCH + mc)) mc++;
+                ip += mc + MINMATCH;
+            }
+            if (op + 6 + (mc + 240) / 255 > (size_t)cap) goto fail;
+            if (mc >= 15) {
+                dst[token] += 15;
+                mc -= 15;
+                for (; mc >= 255; mc -= 255) dst[op++] = 255;
+                dst[op++] = (uint8_t)mc;
+            } else {
+                dst[token] += (uint8_t)mc;
+            }
+        }
+        anchor = ip;
+        if (ip >= mflimitP1) break;
+        T[hpos(AT(ip - 2), 0)] = ip - 2;
+        {
+            const uint32_t h = hpos(AT(ip), 0);
+            cand = T[h];
+            T[h] = ip;
+            if (cand >= low && cand + DIST_MAX >= ip && rd32(AT(cand)) == rd32(AT(ip))) {
+                token = (uint32_t)op++;
+                dst[token] = 0;
+                goto next_match;
+            }
+        }
+        ip++;
+        fh = hpos(AT(ip), 0);
+    }
+
+last_literals:
+    {
+        const size_t run = (size_t)(end - anchor);
+        if (op + run + 1 + (run + 240) / 255 > (size_t)cap) goto fail;
+        if (run >= 15) {
+            size_t acc = run - 15;
+            dst[op++] = 15 << 4;
+            for (; acc >= 255; acc -= 255) dst[op++] = 255;
+            dst[op++] = (uint8_t)acc;
+        } else {
+            dst[op++] = (uint8_t)(run << 4);
+        }
+        memcpy(dst + op, AT(anchor), run);
+        op += run;
+    }
+    result = (int)op;
+fail:
+    free(T);
+    return result;
+#undef AT
+}
+
+/* ===================================================================== */
 /* LZ4 1.9.3 LZ4_decompress_safe (endOnInputSize, full block, noDict,    */
 /* LZ4_FAST_DEC_LOOP=1 as built for x86-64).  lz4mt calls it with        */
 /* cap = blockMax (ref src/lz4mt.cpp:644-646; src/main.cpp:774).         */
@@ -276,7 +430,20 @@ static inline unsigned in8(const uint8_t* src, sll n, sll i) { return (i >= 0 &&
  * LZ4_decompress_safe_withPrefix64k (lowPrefix = dst - 64 KB; then no offset
  * can point before it, and the fast-copy test `dict == withPrefix64k ||
  * match >= lowPrefix` is the same comparison). */
-static int decompress_generic(const uint8_t* src, uint8_t* dst, int srcSize, int outputSize, sll lowP) {
+/* LZ4_decompress_safe_usingDict with the dictionary away from dst
+ * (forceExtDict) differs in three places.  lowP = -dictSize below 64 KiB
+ * (no offset is checked from 64 KiB up: none reaches further than 65535).
+ * inLow = 0: the two short-match shortcuts are taken only for a match
+ * inside the block (`match >= lowPrefix`), so a match that starts in the
+ * dictionary always reaches the copy below, with its end-of-block test.
+ * dictEnd != NULL: positions below 0 are the dictionary's last bytes, and
+ * a match that runs over its end goes on at dst[0] (ext_copy). */
+static void ext_copy(uint8_t* dst, sll op, sll match, sll len, const uint8_t* dictEnd) {
+    for (sll i = 0; i < len; i++) dst[op + i] = match + i < 0 ? dictEnd[match + i] : dst[match + i];
+}
+
+static int decompress_generic(const uint8_t* src, uint8_t* dst, int srcSize, int outputSize, sll lowP, sll inLow,
+                              const uint8_t* dictEnd) {
     if (src == NULL) return -1;
     const sll N = srcSize;
     sll ip = 0, op = 0, cpy, match;
@@ -323,7 +490,7 @@ static int decompress_generic(const uint8_t* src, uint8_t* dst, int srcSize, int
         } else {
             length += MINMATCH;
             if (op + (sll)length >= oend - 64) goto safe_match_copy;
-            if (match >= lowP && offset >= 8) {
+            if (match >= inLow && offset >= 8) {
                 lz77_copy(dst, op, match, (sll)length);
                 op += (sll)length;
                 continue;
@@ -331,6 +498,12 @@ static int decompress_generic(const uint8_t* src, uint8_t* dst, int srcSize, int
         }
         if (match < lowP) goto output_error;
         cpy = op + (sll)length;
+        if (dictEnd && match < 0) {
+            if (cpy > oend - LASTLITERALS) goto output_error;
+            ext_copy(dst, op, match, (sll)length, dictEnd);
+            op = cpy;
+            continue;
+        }
         lz77_copy(dst, op, match, (sll)length);
         op = cpy;
     }
@@ -346,7 +519,7 @@ safe_decode:
             offset = in8(src, N, ip) | (in8(src, N, ip + 1) << 8);
             ip += 2;
             match = op - (sll)offset;
-            if (length != 15 && offset >= 8 && match >= lowP) {
+            if (length != 15 && offset >= 8 && match >= inLow) {
                 lz77_copy(dst, op, match, (sll)length + MINMATCH);
                 op += (sll)length + MINMATCH;
                 continue;
@@ -387,6 +560,12 @@ safe_decode:
     safe_match_copy:
         if (match < lowP) goto output_error;
         cpy = op + (sll)length;
+        if (dictEnd && match < 0) {
+            if (cpy > oend - LASTLITERALS) goto output_error;
+            ext_copy(dst, op, match, (sll)length, dictEnd);
+            op = cpy;
+            continue;
+        }
         if (cpy > oend - 12 && cpy > oend - LASTLITERALS) goto output_error;
         lz77_copy(dst, op, match, (sll)length);
         op = cpy;
@@ -398,13 +577,23 @@ output_error:
 }
 
 int orc_lz4_decompress_safe(const uint8_t* src, uint8_t* dst, int srcSize, int outputSize) {
-    return decompress_generic(src, dst, srcSize, outputSize, 0);
+    return decompress_generic(src, dst, srcSize, outputSize, 0, 0, NULL);
 }
 
 /* LZ4_decompress_safe_withPrefix64k (lz4 1.9.3): the 64 KiB before dst are
  * readable history (ref src/lz4mt.cpp:813-818, block-dependent frames). */
 int orc_lz4_decompress_safe_prefix64k(const uint8_t* src, uint8_t* dst, int srcSize, int outputSize) {
-    return decompress_generic(src, dst, srcSize, outputSize, -65536);
+    return decompress_generic(src, dst, srcSize, outputSize, -65536, -65536, NULL);
+}
+
+/* LZ4_decompress_safe_usingDict (lz4 1.9.3), dictionary not adjacent to dst:
+ * without a dictionary it is LZ4_decompress_safe, otherwise the forceExtDict
+ * decode over the whole dictionary (the decoder does not trim it). */
+int orc_lz4_decompress_safe_usingDict(const uint8_t* src, uint8_t* dst, int srcSize, int outputSize,
+                                      const uint8_t* dict, int dictSize) {
+    if (dictSize <= 0 || dict == NULL) return decompress_generic(src, dst, srcSize, outputSize, 0, 0, NULL);
+    return decompress_generic(src, dst, srcSize, outputSize, dictSize < 65536 ? -(sll)dictSize : -65536, 0,
+                              dict + dictSize);
 }
 
 /* ===================================================================== */

@@ -13,6 +13,10 @@
  *     LZ4_versionNumber() == 10903), see DESIGN.md "Oracle".
  *   - LZ4 1.9.3 LZ4_decompress_safe including its fast/safe loop split, so
  *     accept/reject decisions and negative return values match exactly.
+ *   - LZ4 1.9.3 LZ4_loadDict + LZ4_compress_fast_continue and
+ *     LZ4_decompress_safe_usingDict with the dictionary in a buffer of its
+ *     own: the batched dictionary operators' codec (include/lz4mt_hip.h 5b),
+ *     pinned by tests/test_oracle_dict.py.
  *   - XXH32 (xxhash, seed 0 everywhere in lz4mt: src/lz4mt.cpp:23).
  *   - The lz4mt frame writer/reader for independent blocks
  *     (src/lz4mt.cpp:335-457, 541-734, 898-1011).
@@ -64,6 +68,16 @@ int64_t orc_bd_hc_body(const uint8_t* src, size_t n, int blockMaxId, int bck, ui
 /* LZ4_decompress_safe_withPrefix64k 1.9.3: dst[-65536..-1] is history. */
 int orc_lz4_decompress_safe_prefix64k(const uint8_t* src, uint8_t* dst,
                                       int srcSize, int cap);
+
+/* LZ4_loadDict on a fresh stream + LZ4_compress_fast_continue(.., 1) 1.9.3,
+ * dictionary and source in buffers of their own (usingExtDict): the block's
+ * size, or 0 when it does not fit `cap`. */
+int orc_lz4_compress_dict(const uint8_t* dict, int dictSize, const uint8_t* src,
+                          uint8_t* dst, int n, int cap);
+/* LZ4_decompress_safe_usingDict 1.9.3 with the dictionary away from dst
+ * (forceExtDict): decoded size, or -(error position)-1. */
+int orc_lz4_decompress_safe_usingDict(const uint8_t* src, uint8_t* dst, int srcSize,
+                                      int cap, const uint8_t* dict, int dictSize);
 
 /* ---- lz4mt frame ------------------------------------------------------- */
 typedef struct {
