@@ -348,6 +348,78 @@ Lz4MtResult lz4mtHipDecompressBatchDict(const void* const* d_srcPtrs, const uint
                                         void* const* d_dstPtrs, const uint32_t* d_dstCaps, int32_t* d_outSizes,
                                         const void* d_dict, uint32_t dictSize, void* stream);
 
+/* ---- 5c. LZ4-HC (levels 3..12) with a shared dictionary --------------------
+ * The dictionary of section 5b under the LZ4-HC parsers of
+ * lz4mtHipCompressBatchEx: what small chunks gain most from.  The blocks are
+ * ordinary LZ4 blocks; lz4mtHipDecompressBatchDict decodes them.
+ *
+ * Compress: bytes and d_outSizes[i] are those of, on lz4 1.9.3, with a fresh
+ * LZ4_createStreamHC() stream per chunk and the dictionary, the source and
+ * the destination in three separate, non-adjacent buffers (lz4hc's
+ * external-dictionary mode),
+ *     LZ4_resetStreamHC_fast(s, level);
+ *     LZ4_loadDictHC(s, dict, dictSize);
+ *     LZ4_compress_HC_continue(s, src_i, dst_i, size_i, cap_i);
+ * -- 0 when the block does not fit (cap_i >= lz4mtHipCompressBound(size_i) is
+ * lz4hc's notLimited path; d_dstCaps == NULL means that bound).  Levels are
+ * 3..12, above 12 counts as 12.  The effective dictionary is the last
+ * min(dictSize, LZ4MT_HIP_DICT_WINDOW) bytes.  These are not the bytes of a
+ * dictionary and chunk laid out in one buffer (lz4hc's prefix mode).
+ * A dictionary shorter than 4 bytes inserts nothing into lz4hc's tables and
+ * gives the bytes of lz4mtHipCompressBatchEx at the same level (pinned
+ * against liblz4 for the fixture's inputs, tests/golden/make_golden_dict_hc.py).
+ * One point where liblz4 itself is not defined by its inputs: the optimal
+ * parser (levels 10..12) can reach one of the dictionary's last three
+ * positions as a match candidate, and lz4hc 1.9.3 then compares four bytes of
+ * which up to three lie past the dictionary's end.  Here such a candidate
+ * never matches, and no byte outside the dictionary is read; that is liblz4's
+ * answer whenever the bytes behind its dictionary buffer do not happen to
+ * continue the chunk.
+ *
+ * State: lz4mtHipDictStateSizeHC() bytes (a constant, a multiple of 256:
+ * 32 768 hash heads, 65 536 chain links, a header and padding), opaque,
+ * 256-byte aligned.  lz4mtHipDictPrepareHC builds it with one kernel,
+ * asynchronously: what LZ4_loadDictHC leaves behind (the hash heads, the chain
+ * links of the effective dictionary's inserted positions 0 .. size - 4, the
+ * effective size).  It does not depend on the level: one state serves levels
+ * 3..12.  It is not the state of section 5b, and neither call takes the
+ * other's: lz4mtHipCompressBatchDictHC given a state built by
+ * lz4mtHipDictPrepare, or lz4mtHipCompressBatchDict given one built by
+ * lz4mtHipDictPrepareHC, refuses every chunk (LZ4MT_HIP_BATCH_BAD_CHUNK,
+ * nothing written; decided on the device).  The same happens when the
+ * effective size of dictSize differs from the one the state records (the
+ * stale-state guard of section 5b).
+ * The dictionary may stand at any alignment and end on the last byte of its
+ * allocation; no byte outside its effective part, and no byte outside a
+ * chunk, is read.
+ *
+ * Workspace: lz4mtHipCompressBatchDictWorkspaceSize(maxChunkBytes, nChunks,
+ * level) -- slots, rounds and rules as lz4mtHipCompressBatchEx: any 256-byte
+ * aligned workspace of at least one slot (the size for nChunks = 1) is
+ * accepted, min(workspaceSize / slot, LZ4MT_HIP_BATCH_HC_SLOTS) slots are
+ * used in ceil(nChunks / slots) rounds; a smaller workspace costs time, never
+ * bytes.  The memory contract and the refused chunks are those of
+ * lz4mtHipCompressBatch.  Asynchronous and graph-capturable: no allocation,
+ * no synchronisation, no host read of device memory, no environment variable.
+ *
+ * LZ4MT_RESULT_BAD_ARG, in this order: a null array with nChunks > 0
+ * (d_dstCaps may be null); maxChunkBytes above the maximum; level < 3 (the
+ * fast codec has its own call and its own state); a null d_dict with
+ * dictSize > 0; a state that is null, not 256-byte aligned or (prepare)
+ * smaller than the state size; with nChunks > 0 a workspace that is null, not
+ * 256-byte aligned or smaller than one slot.  Then LZ4MT_RESULT_ERROR without
+ * a HIP device or on a launch error; else LZ4MT_RESULT_OK (nChunks == 0
+ * launches nothing). */
+uint64_t lz4mtHipDictStateSizeHC(void);
+Lz4MtResult lz4mtHipDictPrepareHC(const void* d_dict, uint32_t dictSize, void* d_state, uint64_t stateSize,
+                                  void* stream);
+uint64_t lz4mtHipCompressBatchDictWorkspaceSize(uint32_t maxChunkBytes, uint32_t nChunks, int level);
+Lz4MtResult lz4mtHipCompressBatchDictHC(const void* const* d_srcPtrs, const uint32_t* d_srcSizes,
+                                        uint32_t maxChunkBytes, uint32_t nChunks, void* const* d_dstPtrs,
+                                        const uint32_t* d_dstCaps, int32_t* d_outSizes, const void* d_dict,
+                                        uint32_t dictSize, const void* d_stateHC, int level, void* d_workspace,
+                                        uint64_t workspaceSize, void* stream);
+
 /* ---- 6. diagnostics ----------------------------------------------------- */
 /* Runs s_memtime-stamped twins of the encode / decode kernels (never the
  * product launch) and sums per-phase shader cycles over all blocks.

@@ -30,6 +30,7 @@ __all__ = [
     "batch_compress_bound", "compress_batch", "decompress_batch", "BATCH_MAX_CHUNK", "BATCH_BAD_CHUNK",
     "batch_compress_workspace", "BATCH_HC_SLOTS",
     "DICT_WINDOW", "PreparedDict", "prepare_dict", "compress_batch_dict", "decompress_batch_dict",
+    "prepare_dict_hc", "compress_batch_dict_hc", "batch_compress_dict_workspace",
 ]
 
 lib = _abi.load()
@@ -190,7 +191,7 @@ def _batch(fn_name, srcs, caps, null_caps, max_chunk, stream, level=0, workspace
     ``level`` >= 3 (compress only): lz4mtHipCompressBatchEx, its workspace
     allocated here on the call's stream unless one is given.
     ``dict_args`` (the dictionary calls): the arguments between d_outSizes
-    and the stream, as ctypes values."""
+    and the stream (with ``level`` >= 3: and the level), as ctypes values."""
     n = len(srcs)
     dev = srcs[0].device if n else torch.device("cuda", torch.cuda.current_device())
     if stream is None:
@@ -227,6 +228,17 @@ def _batch(fn_name, srcs, caps, null_caps, max_chunk, stream, level=0, workspace
         st = ctypes.c_void_p(ts.cuda_stream)
         cap_arg = ctypes.c_void_p(None if null_caps else d_cap)
         if level >= 3:
+            if dict_args is not None:   # (dictionary, size, HC state): section 5c
+                if workspace is None:
+                    workspace = batch_compress_dict_workspace(max_chunk, n, level, device=dev)
+                fn_name = "lz4mtHipCompressBatchDictHC"
+                r = lib.lz4mtHipCompressBatchDictHC(ctypes.c_void_p(d_src), ctypes.c_void_p(d_sz), max_chunk, n,
+                                                    ctypes.c_void_p(d_dst), cap_arg, ctypes.c_void_p(sizes.data_ptr()),
+                                                    *dict_args, level, ctypes.c_void_p(workspace.data_ptr()),
+                                                    workspace.numel(), st)
+                if r != Result.OK:
+                    raise Lz4MtError(r, fn_name)
+                return [back[o:o + c] for o, c in zip(offs, caps)], sizes
             if workspace is None:
                 workspace = batch_compress_workspace(max_chunk, n, level, device=dev)
             fn_name = "lz4mtHipCompressBatchEx"
@@ -298,16 +310,32 @@ class PreparedDict:
     """A dictionary ready for compress_batch_dict: ``dictionary`` (the
     caller's uint8 device tensor, kept alive here) and ``state`` (the
     lz4mtHipDictPrepare state, a uint8 device tensor of
-    lz4mtHipDictStateSize bytes)."""
-    __slots__ = ("dictionary", "state")
+    lz4mtHipDictStateSize bytes).  ``kind``: "fast" (lz4mtHipDictPrepare, for
+    compress_batch_dict) or "hc" (lz4mtHipDictPrepareHC, a state of
+    lz4mtHipDictStateSizeHC bytes, for compress_batch_dict_hc); ``is_hc``
+    tells them apart."""
+    __slots__ = ("dictionary", "state", "kind")
 
-    def __init__(self, dictionary, state):
+    def __init__(self, dictionary, state, kind="fast"):
         self.dictionary = dictionary
         self.state = state
+        self.kind = kind
+
+    @property
+    def is_hc(self):
+        return self.kind == "hc"
 
 
 def _dict_ptr(dictionary):
     return ctypes.c_void_p(dictionary.data_ptr() if dictionary.numel() else None), dictionary.numel()
+
+
+def batch_compress_dict_workspace(max_chunk, n, level, device=None):
+    """Scratch for compress_batch_dict_hc at ``level``
+    (lz4mtHipCompressBatchDictWorkspaceSize bytes; empty below level 3): the
+    slots and rounds of batch_compress_workspace."""
+    nbytes = int(lib.lz4mtHipCompressBatchDictWorkspaceSize(int(max_chunk), int(n), int(level)))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device or "cuda")
 
 
 def prepare_dict(dictionary, stream=None):
@@ -315,6 +343,20 @@ def prepare_dict(dictionary, stream=None):
     LZ4_loadDict leaves for ``dictionary`` (a contiguous uint8 device tensor
     of any size and alignment; its last 64 KiB count, fewer than 8 bytes are
     no dictionary).  Returns a PreparedDict.  Does not synchronise."""
+    return _prepare_dict(dictionary, stream, False)
+
+
+def prepare_dict_hc(dictionary, stream=None):
+    """lz4mtHipDictPrepareHC: the same for compress_batch_dict_hc -- what
+    LZ4_loadDictHC leaves (the last 64 KiB count, whatever their number).  The
+    one state serves every level from 3 up.  Returns a PreparedDict of kind
+    "hc".  Does not synchronise."""
+    return _prepare_dict(dictionary, stream, True)
+
+
+def _prepare_dict(dictionary, stream, hc):
+    size_fn, prep_fn = (lib.lz4mtHipDictStateSizeHC, lib.lz4mtHipDictPrepareHC) if hc else \
+        (lib.lz4mtHipDictStateSize, lib.lz4mtHipDictPrepare)
     _check_dev(dictionary, "dictionary")
     if dictionary.numel() >= 1 << 32:
         raise ValueError("a dictionary is at most 2^32 - 1 bytes")
@@ -326,13 +368,12 @@ def prepare_dict(dictionary, stream=None):
     else:
         ts = torch.cuda.ExternalStream(int(stream), device=dev)
     with torch.cuda.stream(ts):
-        state = torch.empty(int(lib.lz4mtHipDictStateSize()), dtype=torch.uint8, device=dev)
+        state = torch.empty(int(size_fn()), dtype=torch.uint8, device=dev)
         dptr, dsize = _dict_ptr(dictionary)
-        r = lib.lz4mtHipDictPrepare(dptr, dsize, ctypes.c_void_p(state.data_ptr()), state.numel(),
-                                    ctypes.c_void_p(ts.cuda_stream))
+        r = prep_fn(dptr, dsize, ctypes.c_void_p(state.data_ptr()), state.numel(), ctypes.c_void_p(ts.cuda_stream))
     if r != Result.OK:
-        raise Lz4MtError(r, "lz4mtHipDictPrepare")
-    return PreparedDict(dictionary, state)
+        raise Lz4MtError(r, "lz4mtHipDictPrepareHC" if hc else "lz4mtHipDictPrepare")
+    return PreparedDict(dictionary, state, "hc" if hc else "fast")
 
 
 def compress_batch_dict(chunks, prepared, caps=None, stream=None):
@@ -342,9 +383,32 @@ def compress_batch_dict(chunks, prepared, caps=None, stream=None):
     compress_batch does; decode with decompress_batch_dict and the same
     dictionary.  Does not synchronise: ``chunks`` and ``prepared`` must stay
     alive until ``stream`` has run the call, and ``stream`` must be ordered
-    after the one prepare_dict ran on."""
+    after the one prepare_dict ran on.  A PreparedDict of kind "hc"
+    (prepare_dict_hc) is a TypeError: LZ4-HC is compress_batch_dict_hc."""
+    return _compress_batch_dict(chunks, prepared, caps, stream, 0, None)
+
+
+def compress_batch_dict_hc(chunks, prepared, level, caps=None, stream=None, workspace=None):
+    """lz4mtHipCompressBatchDictHC: compress_batch at ``level`` 3..12 (LZ4-HC)
+    with the dictionary of ``prepared`` (prepare_dict_hc; a PreparedDict of
+    kind "fast" is a TypeError) before every chunk: the bytes of
+    LZ4_loadDictHC + LZ4_compress_HC_continue.  Everything else as
+    compress_batch_dict; ``workspace`` as for compress_batch
+    (batch_compress_dict_workspace; by default one of the full size is
+    allocated on the call's stream)."""
+    level = int(level)
+    if level < 3:
+        raise ValueError("compress_batch_dict_hc: level 3..12 (the fast codec is compress_batch_dict)")
+    return _compress_batch_dict(chunks, prepared, caps, stream, level, workspace)
+
+
+def _compress_batch_dict(chunks, prepared, caps, stream, level, workspace):
     if not isinstance(prepared, PreparedDict):
-        raise TypeError("prepared must come from prepare_dict")
+        raise TypeError("prepared must come from prepare_dict / prepare_dict_hc")
+    if prepared.is_hc != (level >= 3):
+        raise TypeError("compress_batch_dict takes a prepare_dict state, compress_batch_dict_hc a prepare_dict_hc state")
+    if workspace is not None:
+        _check_dev(workspace, "workspace")
     chunks = list(chunks)
     for i, c in enumerate(chunks):
         _check_dev(c, f"chunks[{i}]")
@@ -355,11 +419,11 @@ def compress_batch_dict(chunks, prepared, caps=None, stream=None):
     dict_args = (dptr, dsize, ctypes.c_void_p(prepared.state.data_ptr()))
     if caps is None:
         return _batch("lz4mtHipCompressBatchDict", chunks, [batch_compress_bound(c.numel()) for c in chunks], True,
-                      big, stream, dict_args=dict_args)
+                      big, stream, level, workspace, dict_args=dict_args)
     caps = [int(c) for c in caps]
     if len(caps) != len(chunks) or any(c < 0 or c >= 1 << 32 for c in caps):
         raise ValueError("caps: one capacity of 0 .. 2^32 - 1 per chunk")
-    return _batch("lz4mtHipCompressBatchDict", chunks, caps, False, big, stream, dict_args=dict_args)
+    return _batch("lz4mtHipCompressBatchDict", chunks, caps, False, big, stream, level, workspace, dict_args=dict_args)
 
 
 def decompress_batch_dict(blocks, caps, dictionary, stream=None):

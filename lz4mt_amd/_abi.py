@@ -106,6 +106,11 @@ PROTOTYPES = {
                                           c_void_p, c_uint32, c_void_p, c_void_p]),
     "lz4mtHipDecompressBatchDict": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_uint32, c_void_p]),
+    "lz4mtHipDictStateSizeHC": (c_uint64, []),
+    "lz4mtHipDictPrepareHC": (c_int, [c_void_p, c_uint32, c_void_p, c_uint64, c_void_p]),
+    "lz4mtHipCompressBatchDictWorkspaceSize": (c_uint64, [c_uint32, c_uint32, c_int]),
+    "lz4mtHipCompressBatchDictHC": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_uint32, c_void_p, c_int, c_void_p, c_uint64, c_void_p]),
     "lz4mtHipFrameBound": (c_uint64, [c_uint64, SD_P]),
     "lz4mtHipCompressWorkspaceSize": (c_uint64, [c_uint64, SD_P]),
     "lz4mtHipCompressFrame": (c_int, [c_void_p, c_uint64, c_void_p, c_uint64, ctypes.POINTER(c_uint64), SD_P,

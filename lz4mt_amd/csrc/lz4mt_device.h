@@ -254,6 +254,21 @@ uint64_t hc_batch_slot_bytes(uint32_t maxChunk, int level);
 hipError_t launch_encode_hc_batch(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
                                   uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps,
                                   int32_t* outSizes, int level, uint8_t* ws, uint32_t slots, hipStream_t st);
+// The same with a shared dictionary (section 5c; k_hc_dict_prepare,
+// k_hc_prev_batch_dict, k_encode_hc_batch_dict / k_encode_hc_opt_batch_dict).
+// LZ4_loadDictHC keeps the last 64 KiB whatever their number (below 4 bytes
+// nothing is inserted, but the bytes still stand before the chunk).  The
+// prepared state serves every level; its layout is lz4mt_hc.hip's.
+constexpr uint32_t kHcDictMagic = 0x4C7E4843u;
+constexpr uint32_t kHcDictHeadsAt = 16384 + 256;                       // behind the fast state's extent
+constexpr uint32_t kHcDictLinksAt = kHcDictHeadsAt + (4u << 15);
+constexpr uint32_t kHcDictStateBytes = kHcDictLinksAt + 2 * (kDictWindow + 128);
+inline uint32_t hc_dict_effective(uint32_t dictSize) { return dictSize < kDictWindow ? dictSize : kDictWindow; }
+hipError_t launch_hc_dict_prepare(const uint8_t* dictEnd, uint32_t E, uint8_t* state, hipStream_t st);
+hipError_t launch_encode_hc_batch_dict(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
+                                       uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps,
+                                       int32_t* outSizes, const uint8_t* dictEnd, uint32_t E, const uint8_t* state,
+                                       int level, uint8_t* ws, uint32_t slots, hipStream_t st);
 // -BD at level >= 3: segments [begin[k], end[k]) of src (begin >= -64 KiB),
 // blockSeg[b] = block b's segment; delta0 = chain scratch for src[0], with
 // 64 Ki entries before it.

@@ -652,6 +652,49 @@ extern "C" Lz4MtResult lz4mtHipDecompressBatchDict(const void* const* d_srcPtrs,
     return LZ4MT_RESULT_OK;
 }
 
+// LZ4-HC with a shared dictionary (section 5c).  As above the host only trims
+// the dictionary; the state's kind and recorded size are checked on the device.
+extern "C" uint64_t lz4mtHipDictStateSizeHC(void) { return kHcDictStateBytes; }
+
+extern "C" Lz4MtResult lz4mtHipDictPrepareHC(const void* d_dict, uint32_t dictSize, void* d_state, uint64_t stateSize,
+                                             void* stream) {
+    if (!d_dict && dictSize > 0) return LZ4MT_RESULT_BAD_ARG;
+    if (!d_state || (reinterpret_cast<uintptr_t>(d_state) & 255) != 0 || stateSize < kHcDictStateBytes)
+        return LZ4MT_RESULT_BAD_ARG;
+    if (!have_device()) return LZ4MT_RESULT_ERROR;
+    HIPCHK(launch_hc_dict_prepare(static_cast<const uint8_t*>(d_dict) + dictSize, hc_dict_effective(dictSize),
+                                  static_cast<uint8_t*>(d_state), static_cast<hipStream_t>(stream)));
+    return LZ4MT_RESULT_OK;
+}
+
+extern "C" uint64_t lz4mtHipCompressBatchDictWorkspaceSize(uint32_t maxChunkBytes, uint32_t nChunks, int level) {
+    return lz4mtHipCompressBatchWorkspaceSize(maxChunkBytes, nChunks, level);   // the same slots
+}
+
+extern "C" Lz4MtResult lz4mtHipCompressBatchDictHC(const void* const* d_srcPtrs, const uint32_t* d_srcSizes,
+                                                   uint32_t maxChunkBytes, uint32_t nChunks, void* const* d_dstPtrs,
+                                                   const uint32_t* d_dstCaps, int32_t* d_outSizes, const void* d_dict,
+                                                   uint32_t dictSize, const void* d_stateHC, int level,
+                                                   void* d_workspace, uint64_t workspaceSize, void* stream) {
+    if (nChunks && (!d_srcPtrs || !d_srcSizes || !d_dstPtrs || !d_outSizes)) return LZ4MT_RESULT_BAD_ARG;
+    if (maxChunkBytes > LZ4MT_HIP_BATCH_MAX_CHUNK) return LZ4MT_RESULT_BAD_ARG;
+    if (level < 3) return LZ4MT_RESULT_BAD_ARG;
+    if (!d_dict && dictSize > 0) return LZ4MT_RESULT_BAD_ARG;
+    if (!d_stateHC || (reinterpret_cast<uintptr_t>(d_stateHC) & 255) != 0) return LZ4MT_RESULT_BAD_ARG;
+    const uint64_t slot = hc_batch_slot_bytes(maxChunkBytes, level);
+    if (nChunks && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0 || workspaceSize < slot))
+        return LZ4MT_RESULT_BAD_ARG;
+    if (!have_device()) return LZ4MT_RESULT_ERROR;
+    if (nChunks == 0) return LZ4MT_RESULT_OK;
+    const uint32_t slots = (uint32_t)std::min<uint64_t>(workspaceSize / slot, kHcBatchSlots);
+    HIPCHK(launch_encode_hc_batch_dict(reinterpret_cast<const uint8_t* const*>(d_srcPtrs), d_srcSizes, maxChunkBytes,
+                                       nChunks, reinterpret_cast<uint8_t* const*>(d_dstPtrs), d_dstCaps, d_outSizes,
+                                       static_cast<const uint8_t*>(d_dict) + dictSize, hc_dict_effective(dictSize),
+                                       static_cast<const uint8_t*>(d_stateHC), level,
+                                       static_cast<uint8_t*>(d_workspace), slots, static_cast<hipStream_t>(stream)));
+    return LZ4MT_RESULT_OK;
+}
+
 // ===========================================================================
 // 2. device-resident frame engine
 // ===========================================================================

@@ -98,9 +98,29 @@ __device__ __forceinline__ v4u hc_chunk_load(g_cu8* s, uint32_t n, uint32_t c0, 
 // position without a predecessor in its own wave sees the earlier waves'
 // positions.  The source goes through an 8 KiB LDS ring, one 4 KiB chunk
 // (16 steps) at a time, the next chunk's load in flight meanwhile.
-__device__ void hc_prev_range(g_cu8* s, uint32_t n, g_u16* dl, l_u32* last, l_u8* dd, l_u32* ring) {
+// MODE (the dictionary batch, section 5c of lz4mt_hip.h):
+//   kPrevPlain  as above.
+//   kPrevDict   the range is a dictionary (k_hc_dict_prepare): dl[p] as lz4hc's
+//               chainTable holds it, 65535 instead of 0 for "none"; `last` is
+//               left complete for the caller (the hash heads).
+//   kPrevChunk  the range is a chunk behind a dictionary of `base0` bytes:
+//               positions count from the dictionary's start (chunk byte p is
+//               position base0 + p), `last` starts from the dictionary's heads
+//               (32768 words, position + 1) instead of empty, so a delta may
+//               reach into the dictionary; the 65535 cap applies to positions.
+enum : int { kPrevPlain = 0, kPrevDict = 1, kPrevChunk = 2 };
+template <int MODE = kPrevPlain>
+__device__ void hc_prev_range(g_cu8* s, uint32_t n, g_u16* dl, l_u32* last, l_u8* dd, l_u32* ring,
+                              const uint32_t* heads = nullptr, uint32_t base0 = 0) {
     const uint32_t t = threadIdx.x, L = laneid(), wv = t >> 6;
-    for (uint32_t i = t; i < (1u << kHashLog); i += kPrevThreads) last[i] = 0;
+    const uint32_t pb = MODE == kPrevChunk ? base0 : 0u;   // position of s[0]
+    if (MODE == kPrevChunk) {
+        typedef __attribute__((address_space(3))) v4u l_v4;
+        const __attribute__((address_space(1))) v4u* hv = (const __attribute__((address_space(1))) v4u*)heads;
+        for (uint32_t i = t; i < (1u << kHashLog) / 4; i += kPrevThreads) ((l_v4*)last)[i] = hv[i];
+    } else {
+        for (uint32_t i = t; i < (1u << kHashLog); i += kPrevThreads) last[i] = 0;
+    }
     if (n < 4) return;
     const uint32_t np = n - 3;   // positions with 4 readable bytes
     const bool al = ((uintptr_t)s & 15) == 0;
@@ -140,16 +160,18 @@ __device__ void hc_prev_range(g_cu8* s, uint32_t n, g_u16* dl, l_u32* last, l_u8
                 pending &= ~m;
             }
             const bool groupLast = live && !(gm & ~((2ull << L) - 1ull));
-            uint32_t q1 = pred >= 0 ? base + 64 * wv + (uint32_t)pred + 1 : 0u;   // position + 1 of the previous
+            uint32_t q1 = pred >= 0 ? pb + base + 64 * wv + (uint32_t)pred + 1 : 0u;   // position + 1 of the previous
             for (uint32_t u = 0; u < kPrevThreads / 64; ++u) {
                 if (wv == u) {
                     if (live && pred < 0) q1 = last[h];
                     WAVE_SYNC();
-                    if (groupLast) last[h] = p + 1;
+                    if (groupLast) last[h] = pb + p + 1;
                 }
                 __syncthreads();
             }
-            if (live) dl[p] = (uint16_t)((q1 && p + 1 - q1 <= kHcDist) ? p + 1 - q1 : 0u);
+            if (live)
+                dl[p] = (uint16_t)((q1 && pb + p + 1 - q1 <= kHcDist) ? pb + p + 1 - q1
+                                                                       : (MODE == kPrevDict ? kHcDist : 0u));
         }
         nxt = hc_chunk_load(s, n, c0 + 8192, al);
     }
@@ -193,6 +215,7 @@ struct HcBlock {
     g_cu16* dl;           // k_hc_prev output
     uint32_t maxAttempts;
     bool pattern;         // pattern analysis (level 9)
+    static constexpr uint32_t kOptMin = 13;   // hc_opt_parse: smaller fresh blocks have no match
 
     // chain delta as lz4hc's chainTable holds it (capped 65535 = "none")
     __device__ __forceinline__ uint32_t chain(uint32_t m) const {
@@ -365,6 +388,250 @@ struct HcBlock {
     }
 };
 
+// A chunk behind an external dictionary (lz4mt_hip.h section 5c): lz4hc 1.9.3
+// after LZ4_loadDictHC + LZ4HC_setExternalDict, dictionary and chunk in
+// buffers of their own.  Restated on the host in tools/lz4hc_dict_model.c
+// (pinned against liblz4 by tools/lz4hc_dict_diff.py); this is its port.
+// Positions count from the effective dictionary's start: dict[P] for P in
+// [0, E), chunk byte p at position E + p (lz4hc's index is position + 64 KiB,
+// lowLimit = 0, dictLimit = E here).  The parsers work in chunk offsets; a
+// match position leaves wider() minus E (wrapping below 0 for one in the
+// dictionary), so `ip - ref` is its offset either way.
+//   dl   the chunk's deltas (k_hc_prev_batch_dict: distance in positions, so a
+//        link may reach into the dictionary; 0 = none within 65535)
+//   ddl  the dictionary's links as lz4hc's chainTable holds them (65535 =
+//        none, 0 = never inserted: its last three positions)
+// What differs from a prefix (one buffer): a chunk-side candidate counts back
+// to the chunk's start only; a dictionary-side one has no 16-bit pre-filter,
+// counts forward to the dictionary's end and on from the chunk's start, and
+// back to the dictionary's start; the byte runs of pattern analysis cross the
+// boundary both ways and LZ4HC_protectDictEnd keeps its candidates off the
+// dictionary's last three positions.
+struct HcDictBlock {
+    g_cu8* s;             // chunk
+    uint32_t n;
+    g_cu16* dl;
+    g_cu8* dict;          // effective dictionary's first byte
+    g_cu16* ddl;
+    uint32_t E;
+    uint32_t maxAttempts;
+    bool pattern;
+    static constexpr uint32_t kOptMin = 12;   // LZ4HC_compress_optimal has no LZ4_minLength test: a 12-byte
+                                              // chunk is searched at its first byte (the dictionary may match)
+
+    // lz4hc's chainTable value at position q (q < E + n + 64: the slot's pad)
+    __device__ __forceinline__ uint32_t link(uint32_t q) const {
+        if (q < E) return ddl[q];
+        const uint32_t d = dl[q - E];
+        return d ? d : kHcDist;
+    }
+    // LZ4HC_protectDictEnd
+    __device__ __forceinline__ bool protect(uint32_t P) const { return (uint32_t)((E - 1) - P) >= 3; }
+    // four bytes of the dictionary at m, the ones past its end as 0 (never read)
+    __device__ __forceinline__ uint32_t rd32_dict(uint32_t m) const {
+        if (m + 4 <= E) return rd32(dict + m);
+        uint32_t v = 0;
+        for (uint32_t i = 0; i < 4; ++i)
+            if (m + i < E) v |= (uint32_t)dict[m + i] << (8 * i);
+        return v;
+    }
+    // equal bytes of the chunk's [a, limit) and B[b, ...), 256 per round; dictSide: B is the dictionary
+    // (the caller's limit keeps b + (limit - a) <= E), else the chunk
+    __device__ uint32_t count_fwd(uint32_t a, uint32_t b, uint32_t limit, bool dictSide) const {
+        const uint32_t L = laneid();
+        uint32_t c = 0;
+        for (;;) {
+            const uint32_t x = a + c + 4 * L;
+            uint32_t eq = 0;
+            if (x < limit) {
+                const uint32_t av = rd32(s + x);
+                const uint32_t bv = dictSide ? rd32_dict(b + c + 4 * L) : rd32(s + b + c + 4 * L);
+                const uint32_t diff = av ^ bv;
+                eq = diff ? ((uint32_t)__builtin_ctz(diff) >> 3) : 4u;
+                eq = min(eq, limit - x);
+            }
+            const uint64_t nf = ballot(eq < 4);
+            if (nf) {
+                const uint32_t f = ffs64(nf);
+                return c + 4 * f + rdlane(eq, (int)f);
+            }
+            c += 256;
+        }
+    }
+    // LZ4HC_countBack of chunk ip against M[match] (M: chunk or dictionary), at most lim steps
+    __device__ int count_back(uint32_t ip, g_cu8* M, uint32_t match, uint32_t lim) const {
+        const uint32_t L = laneid();
+        uint32_t k = 0;
+        for (;;) {
+            const uint32_t j = k + L + 1;
+            const bool same = j <= lim && s[ip - j] == M[match - j];
+            const uint64_t stop = ballot(!same);
+            if (stop != 0) return -(int)(k + ffs64(stop));
+            k += 64;
+        }
+    }
+    // run of byte v in M from p up to end / ending just before p down to low
+    __device__ uint32_t run_fwd(g_cu8* M, uint32_t p, uint32_t end, uint32_t v) const {
+        const uint32_t L = laneid();
+        for (uint32_t c = 0;; c += 64) {
+            const uint32_t x = p + c + L;
+            const uint64_t stop = ballot(!(x < end && M[x] == v));
+            if (stop) return c + ffs64(stop);
+        }
+    }
+    __device__ uint32_t run_back(g_cu8* M, uint32_t p, uint32_t low, uint32_t v) const {
+        const uint32_t L = laneid();
+        for (uint32_t c = 0;; c += 64) {
+            const uint32_t j = c + L + 1;
+            const uint64_t stop = ballot(!(j <= p - low && M[p - j] == v));
+            if (stop) return c + ffs64(stop);
+        }
+    }
+
+    // LZ4HC_InsertAndGetWiderMatch, external dictionary; ip, iLow, iHigh, *spos: chunk offsets
+    template <bool CS = false>
+    __device__ int wider(uint32_t ip, uint32_t iLow, uint32_t iHigh, int longest, uint32_t* mpos,
+                         uint32_t* spos) const {
+        const uint32_t IP = ip + E;
+        const uint32_t lowest = IP > kHcDist ? IP - kHcDist : 0u;
+        const uint32_t lookBack = ip - iLow;
+        int nbAttempts = (int)maxAttempts;
+        const uint32_t pat = rd32(s + ip);
+        const uint32_t pb = pat & 255u;
+        int repeat = 0;   // 0 untested, 1 confirmed, 2 not
+        uint32_t srcPatLen = 0;
+        uint32_t mcp = 0;   // matchChainPos
+        const uint32_t d0 = uni(dl[ip]);
+        if (d0 == 0) return longest;   // no earlier position with this hash in the window
+        uint32_t m = IP - d0;
+        while (m >= lowest && nbAttempts > 0) {
+            --nbAttempts;
+            int matchLength = 0;
+            if (m >= E) {   // in the chunk: as HcBlock::wider, the chunk's start its low limit
+                const uint32_t mc = m - E;
+                const uint32_t f16 = uni(rd16(s + mc - lookBack + (uint32_t)longest - 1));
+                const uint32_t m32 = uni(rd32(s + mc));
+                if (uni(rd16(s + iLow + (uint32_t)longest - 1)) == f16 && m32 == pat) {
+                    const int back = lookBack ? count_back(ip, s, mc, min(lookBack, mc)) : 0;
+                    int ml = 4 + (int)count_fwd(ip + 4, mc + 4, iHigh, false);
+                    ml -= back;
+                    matchLength = ml;
+                    if (ml > longest) {
+                        longest = ml;
+                        *mpos = mc + (uint32_t)back;
+                        *spos = ip + (uint32_t)back;
+                    }
+                }
+            } else if (uni(rd32_dict(m)) == pat && m + 4 <= E) {
+                // in the dictionary.  (One of its last three positions is reached when the chain of
+                // position m + mcp is followed: lz4hc reads up to three bytes past the dictionary
+                // there; here the candidate counts as unequal and nothing past the end is read.)
+                const uint32_t vLimit = min(ip + (E - m), iHigh);
+                int ml = 4 + (int)count_fwd(ip + 4, m + 4, vLimit, true);
+                if (ip + (uint32_t)ml == vLimit && vLimit < iHigh)   // over the dictionary's end: on from the chunk's start
+                    ml += (int)count_fwd(ip + (uint32_t)ml, 0, iHigh, false);
+                const int back = lookBack ? count_back(ip, dict, m, min(lookBack, m)) : 0;
+                ml -= back;
+                matchLength = ml;
+                if (ml > longest) {
+                    longest = ml;
+                    *mpos = m + (uint32_t)back - E;
+                    *spos = ip + (uint32_t)back;
+                }
+            }
+            if (CS && matchLength == longest && m + (uint32_t)longest <= IP) {
+                // a better chain (as HcBlock::wider); the links of a match that runs over the
+                // dictionary's end come from both tables
+                uint32_t dtn = 1;
+                const int end = longest - 4 + 1;
+                int step = 1, accel = 1 << 4;
+                int pos = 0, base = -64;
+                uint32_t lk = 0;
+                while (pos < end) {
+                    if (pos >= base + 64) {   // links of [pos, pos + 64)
+                        base = pos;
+                        lk = link(m + (uint32_t)pos + laneid());
+                    }
+                    const uint32_t cdist = rdlane(lk, pos - base);
+                    step = accel++ >> 4;
+                    if (cdist > dtn) {
+                        dtn = cdist;
+                        mcp = (uint32_t)pos;
+                        accel = 1 << 4;
+                    }
+                    pos += step;
+                }
+                if (dtn > 1) {
+                    if (dtn > m) break;   // below the dictionary: under `lowest`
+                    m -= dtn;
+                    continue;
+                }
+            }
+            const uint32_t distNext = uni(link(m));
+            if (pattern && distNext == 1 && mcp == 0) {
+                const uint32_t cand = m - 1;
+                if (repeat == 0) {
+                    if (((pat & 0xFFFF) == (pat >> 16)) & ((pat & 0xFF) == (pat >> 24))) {
+                        repeat = 1;
+                        srcPatLen = run_fwd(s, ip + 4, iHigh, pb) + 4;
+                    } else {
+                        repeat = 2;
+                    }
+                }
+                if (repeat == 1 && cand >= lowest && protect(cand)) {
+                    const bool ext = cand < E;
+                    const uint32_t cl = cand - E;   // (chunk side)
+                    if (uni(ext ? rd32(dict + cand) : rd32(s + cl)) == pat) {   // good candidate
+                        uint32_t fwdLen, backLen;
+                        if (ext) {
+                            fwdLen = run_fwd(dict, cand + 4, E, pb) + 4;
+                            if (cand + fwdLen == E) fwdLen += run_fwd(s, 0, iHigh, pb);   // on from the chunk's start
+                            backLen = run_back(dict, cand, 0, pb);
+                        } else {
+                            fwdLen = run_fwd(s, cl + 4, iHigh, pb) + 4;
+                            backLen = run_back(s, cl, 0, pb);
+                            if (backLen == cl && E > 0) backLen += run_back(dict, E, 0, pb);   // back from the dictionary's end
+                        }
+                        {
+                            const uint32_t lo = cand - backLen;
+                            backLen = cand - (lo > lowest ? lo : lowest);
+                        }
+                        const uint32_t segLen = backLen + fwdLen;
+                        if (segLen >= srcPatLen && fwdLen <= srcPatLen) {
+                            const uint32_t nm = cand + fwdLen - srcPatLen;
+                            m = protect(nm) ? nm : E;
+                        } else {
+                            const uint32_t nm = cand - backLen;
+                            if (!protect(nm)) {
+                                m = E;
+                            } else {
+                                m = nm;
+                                if (lookBack == 0) {
+                                    const uint32_t maxML = segLen < srcPatLen ? segLen : srcPatLen;
+                                    if ((uint32_t)longest < maxML) {
+                                        if (IP - m > kHcDist) break;
+                                        longest = (int)maxML;
+                                        *mpos = m - E;
+                                        *spos = ip;
+                                    }
+                                    const uint32_t dn = uni(link(m));
+                                    if (dn > m) break;   // below the dictionary: under `lowest`
+                                    m -= dn;
+                                }
+                            }
+                        }
+                        continue;
+                    }
+                }
+            }
+            const uint32_t dfol = mcp ? uni(link(m + mcp)) : distNext;   // follow the current chain
+            if (m < dfol || dfol == 0) break;   // below the dictionary / (0: lz4hc would spend its attempts here)
+            m -= dfol;
+        }
+        return longest;
+    }
+};
+
 // LZ4HC_encodeSequence into d; returns false on overflow (limitedOutput)
 __device__ bool hc_encode(g_cu8* s, g_u8* d, uint32_t& ip, uint32_t& op, uint32_t& anchor, int ml, uint32_t ref,
                           bool limit, uint32_t cap) {
@@ -437,8 +704,8 @@ struct HcHooks {
 // LZ4HC_compress_hashChain from the loop-top state st; returns the state it
 // stops in.  MODE 0: to the block end (last literals; status kHcEnd, or
 // kHcFail when the output does not fit cap); 1 / 2: see HcHooks.
-template <int MODE>
-__device__ HcState hc_parse(const HcBlock& B, g_u8* d, uint32_t cap, bool limit, HcState st, const HcHooks& hk,
+template <int MODE, class BK>
+__device__ HcState hc_parse(const BK& B, g_u8* d, uint32_t cap, bool limit, HcState st, const HcHooks& hk,
                            bool fresh = false) {
     const uint32_t L = laneid();
     const uint32_t n = B.n;
@@ -559,7 +826,8 @@ last_literals : {
 // LZ4HC_compress_hashChain over [start, B.n) of B.s (start > 0: the rest of
 // a stream segment before it, -BD at level >= 3); 0 = does not fit cap
 // (store raw)
-__device__ int32_t encode_block_hc(const HcBlock& B, g_u8* d, uint32_t cap, uint32_t start = 0) {
+template <class BK>
+__device__ int32_t encode_block_hc(const BK& B, g_u8* d, uint32_t cap, uint32_t start = 0) {
     const uint32_t blen = B.n - start;
     const bool limit = (uint64_t)cap < (uint64_t)blen + blen / 255 + 16;
     const HcState r = hc_parse<0>(B, d, cap, limit, HcState{start, start, 0, 0, 0}, HcHooks{}, true);
@@ -605,8 +873,8 @@ __device__ __forceinline__ int hc_seq_price(int litlen, int mlen) {
 // top has the same property: with anchor == ip the literal run is empty, the
 // chain is a function of the input and the price table is rebuilt from ip,
 // so two parses there with the same ip write the same bytes from then on.
-template <int MODE, int AS>
-__device__ HcState hc_opt_parse(const HcBlock& B, g_u8* d, uint32_t cap, bool limit, HcState st, const HcHooks& hk,
+template <int MODE, int AS, class BK>
+__device__ HcState hc_opt_parse(const BK& B, g_u8* d, uint32_t cap, bool limit, HcState st, const HcHooks& hk,
                                 const HcOpt<AS>& O, int suff, bool fullUpdate, bool fresh = false) {
     typedef HcOpt<AS> OT;
     const uint32_t L = laneid();
@@ -619,7 +887,7 @@ __device__ HcState hc_opt_parse(const HcBlock& B, g_u8* d, uint32_t cap, bool li
     // FindLongerMatch: a match longer than minLen at p (pattern analysis and chain swap on)
     auto longer = [&](uint32_t p, int minLen, int& len, int& off) {
         uint32_t mpos = 0, spos = p;
-        const int ml = B.wider<true>(p, p, n - 5, minLen, &mpos, &spos);
+        const int ml = B.template wider<true>(p, p, n - 5, minLen, &mpos, &spos);
         len = ml > minLen ? ml : 0;
         off = ml > minLen ? (int)(spos - mpos) : 0;
     };
@@ -632,7 +900,7 @@ __device__ HcState hc_opt_parse(const HcBlock& B, g_u8* d, uint32_t cap, bool li
         }
         WAVE_SYNC();
     };
-    if (!(fresh && n < 13)) {   // (a fresh block below 13 bytes has no match: straight to the last literals)
+    if (!(fresh && n < BK::kOptMin)) {   // (a fresh block below 13 bytes has no match: straight to the last literals)
         const uint32_t mflimit = n >= 12 ? n - 12 : 0;
         while (ip <= mflimit) {
             if (MODE == 1) {
@@ -785,8 +1053,8 @@ __device__ HcState hc_opt_parse(const HcBlock& B, g_u8* d, uint32_t cap, bool li
 }
 
 // the optimal parse of a whole block; 0 = does not fit cap (store raw)
-template <int AS>
-__device__ int32_t encode_block_hc_opt(const HcBlock& B, g_u8* d, uint32_t cap, const HcOpt<AS>& O, int suff,
+template <int AS, class BK>
+__device__ int32_t encode_block_hc_opt(const BK& B, g_u8* d, uint32_t cap, const HcOpt<AS>& O, int suff,
                                        bool fullUpdate) {
     const bool limit = (uint64_t)cap < (uint64_t)B.n + B.n / 255 + 16;
     const HcState r = hc_opt_parse<0>(B, d, cap, limit, HcState{0, 0, 0, 0, 0}, HcHooks{}, O, suff, fullUpdate, true);
@@ -918,6 +1186,119 @@ __global__ void __launch_bounds__(64) k_encode_hc_opt_batch(const uint8_t* const
     if (!c.bad) {
         uint8_t* slot = ws + (uint64_t)blockIdx.x * slotBytes;
         HcBlock B{c.s, c.n, (g_cu16*)slot, nbSearches, true};   // pattern analysis always on
+        r = encode_block_hc_opt(B, c.d, c.cap, hc_opt_at(slot + tableAt, 0), sufficientLen, fullUpdate != 0);
+    }
+    if (laneid() == 0) outSizes[blockIdx.x] = r;
+}
+
+// ---------------------------------------------------------------------------
+// The same with a shared dictionary (lz4mt_hip.h section 5c,
+// lz4mtHipDictPrepareHC / lz4mtHipCompressBatchDictHC): every chunk is
+// LZ4_loadDictHC(dict) + LZ4_compress_HC_continue(chunk) on a fresh stream,
+// the dictionary in a buffer of its own (HcDictBlock).
+// The state (kHcDictStateBytes, 256-byte aligned), level-independent:
+//   word 0            kHcDictMagic
+//   word 1            E, the effective dictionary size it was built for
+//   word 4096         0xFFFFFFFF: where the fast codec's state (section 5b)
+//                     keeps its size, so lz4mtHipCompressBatchDict refuses
+//                     this state; a fast state has no kHcDictMagic in word 0
+//                     (a table entry: bits 17..22 clear), so it is refused here
+//   kHcDictHeadsAt    32768 words: position + 1 of each hash's latest
+//                     inserted position (0 = none), what LZ4_loadDictHC leaves
+//                     in hashTable
+//   kHcDictLinksAt    65536 + 128 u16: chainTable of positions 0 .. E - 4
+//                     (65535 = no earlier position), 0 from E - 3 on (the last
+//                     three are never inserted; the rest is the pad a 64-wide
+//                     link load may touch)
+// ---------------------------------------------------------------------------
+static_assert(kHcDictHeadsAt % 16 == 0 && kHcDictLinksAt == kHcDictHeadsAt + (4u << kHashLog) &&
+              kHcDictStateBytes == kHcDictLinksAt + 2 * (kDictWindow + 128) && kHcDictStateBytes % 256 == 0 &&
+              kHcDictHeadsAt > 4096 * 4 + 4, "HC dictionary state");
+
+__device__ __forceinline__ bool hc_dict_state_ok(const uint8_t* state, uint32_t E) {
+    const uint32_t* w = (const uint32_t*)state;
+    return w[0] == kHcDictMagic && w[1] == E;
+}
+
+// One workgroup: hc_prev_range over the effective dictionary [dictEnd - E,
+// dictEnd) (read by bytes, or by aligned 16 bytes inside it: nothing outside
+// is read), then the heads and the rest of the state.  Every word of the
+// state is written, each by one thread.
+__global__ void __launch_bounds__(kPrevThreads) k_hc_dict_prepare(const uint8_t* __restrict__ dictEnd, uint32_t E,
+                                                                  uint8_t* __restrict__ state) {
+    __shared__ uint32_t last[1u << kHashLog];
+    __shared__ uint8_t dd[4 * 1024];
+    __shared__ __attribute__((aligned(16))) uint32_t ring[2048];
+    const uint32_t t = threadIdx.x;
+    g_u16* links = (g_u16*)(state + kHcDictLinksAt);
+    hc_prev_range<kPrevDict>((g_cu8*)dictEnd - E, E, links, (l_u32*)last, (l_u8*)dd, (l_u32*)ring);
+    __syncthreads();
+    uint32_t* heads = (uint32_t*)(state + kHcDictHeadsAt);
+    for (uint32_t i = t; i < (1u << kHashLog); i += kPrevThreads) heads[i] = last[i];
+    for (uint32_t p = (E >= 4 ? E - 3 : 0u) + t; p < kDictWindow + 128; p += kPrevThreads) links[p] = 0;
+    uint32_t* w = (uint32_t*)state;
+    for (uint32_t i = t; i < kHcDictHeadsAt / 4; i += kPrevThreads)
+        w[i] = i == 0 ? kHcDictMagic : i == 1 ? E : i == 4096 ? 0xFFFFFFFFu : 0u;
+}
+
+// The chain of every chunk of the round behind the dictionary.  A state that
+// is not an HC state for E ends the workgroup (uniform, before any barrier):
+// the parse kernel refuses the chunk.
+__global__ void __launch_bounds__(kPrevThreads) k_hc_prev_batch_dict(const uint8_t* const* __restrict__ srcPtrs,
+                                                                     const uint32_t* __restrict__ srcSizes,
+                                                                     uint32_t maxChunk,
+                                                                     uint8_t* const* __restrict__ dstPtrs,
+                                                                     uint8_t* __restrict__ ws, uint64_t slotBytes,
+                                                                     const uint8_t* __restrict__ state, uint32_t E) {
+    __shared__ uint32_t last[1u << kHashLog];
+    __shared__ uint8_t dd[4 * 1024];
+    __shared__ __attribute__((aligned(16))) uint32_t ring[2048];
+    const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, nullptr);
+    if (c.bad || !hc_dict_state_ok(state, E)) return;
+    hc_prev_range<kPrevChunk>(c.s, c.n, (g_u16*)(ws + (uint64_t)blockIdx.x * slotBytes), (l_u32*)last, (l_u8*)dd,
+                              (l_u32*)ring, (const uint32_t*)(state + kHcDictHeadsAt), E);
+}
+
+__device__ __forceinline__ HcDictBlock hc_dict_block(const BatchChunk& c, const uint8_t* slot, const uint8_t* dictEnd,
+                                                     uint32_t E, const uint8_t* state, uint32_t attempts,
+                                                     bool pattern) {
+    return HcDictBlock{c.s, c.n, (g_cu16*)slot, (g_cu8*)dictEnd - E, (g_cu16*)(state + kHcDictLinksAt), E, attempts,
+                       pattern};
+}
+
+// Levels 3..9 / 10..12: k_encode_hc_batch / k_encode_hc_opt_batch over HcDictBlock
+__global__ void __launch_bounds__(64) k_encode_hc_batch_dict(const uint8_t* const* __restrict__ srcPtrs,
+                                                             const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
+                                                             uint8_t* const* __restrict__ dstPtrs,
+                                                             const uint32_t* __restrict__ dstCaps,
+                                                             int32_t* __restrict__ outSizes,
+                                                             const uint8_t* __restrict__ ws, uint64_t slotBytes,
+                                                             uint32_t maxAttempts, const uint8_t* __restrict__ dictEnd,
+                                                             uint32_t E, const uint8_t* __restrict__ state) {
+    const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, dstCaps);
+    int32_t r = kBatchBadChunk;
+    if (!c.bad && hc_dict_state_ok(state, E)) {
+        const HcDictBlock B =
+            hc_dict_block(c, ws + (uint64_t)blockIdx.x * slotBytes, dictEnd, E, state, maxAttempts, maxAttempts > 128);
+        r = encode_block_hc(B, c.d, c.cap);
+    }
+    if (laneid() == 0) outSizes[blockIdx.x] = r;
+}
+
+__global__ void __launch_bounds__(64) k_encode_hc_opt_batch_dict(const uint8_t* const* __restrict__ srcPtrs,
+                                                                 const uint32_t* __restrict__ srcSizes,
+                                                                 uint32_t maxChunk, uint8_t* const* __restrict__ dstPtrs,
+                                                                 const uint32_t* __restrict__ dstCaps,
+                                                                 int32_t* __restrict__ outSizes, uint8_t* ws,
+                                                                 uint64_t slotBytes, uint64_t tableAt,
+                                                                 uint32_t nbSearches, int32_t sufficientLen,
+                                                                 int32_t fullUpdate, const uint8_t* __restrict__ dictEnd,
+                                                                 uint32_t E, const uint8_t* __restrict__ state) {
+    const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, dstCaps);
+    int32_t r = kBatchBadChunk;
+    if (!c.bad && hc_dict_state_ok(state, E)) {
+        uint8_t* slot = ws + (uint64_t)blockIdx.x * slotBytes;
+        const HcDictBlock B = hc_dict_block(c, slot, dictEnd, E, state, nbSearches, true);
         r = encode_block_hc_opt(B, c.d, c.cap, hc_opt_at(slot + tableAt, 0), sufficientLen, fullUpdate != 0);
     }
     if (laneid() == 0) outSizes[blockIdx.x] = r;
@@ -1307,6 +1688,43 @@ hipError_t launch_encode_hc_batch(const uint8_t* const* srcPtrs, const uint32_t*
         else
             hipLaunchKernelGGL(k_encode_hc_batch, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, maxChunk,
                                dstPtrs + o, caps, outSizes + o, (const uint8_t*)ws, slotBytes, att);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        o += g;
+    }
+    return hipSuccess;
+}
+
+// The dictionary operators (section 5c).  dictEnd / E: one past the
+// dictionary's last byte and its effective size (hc_dict_effective); state:
+// kHcDictStateBytes, 256-byte aligned.
+hipError_t launch_hc_dict_prepare(const uint8_t* dictEnd, uint32_t E, uint8_t* state, hipStream_t st) {
+    hipLaunchKernelGGL(k_hc_dict_prepare, dim3(1), dim3(kPrevThreads), 0, st, dictEnd, E, state);
+    return hipGetLastError();
+}
+
+// launch_encode_hc_batch's rounds and slots, every chunk behind the dictionary
+hipError_t launch_encode_hc_batch_dict(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
+                                       uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps,
+                                       int32_t* outSizes, const uint8_t* dictEnd, uint32_t E, const uint8_t* state,
+                                       int level, uint8_t* ws, uint32_t slots, hipStream_t st) {
+    if (level < 3 || slots == 0 || !ws || !state) return hipErrorInvalidValue;
+    slots = std::min(slots, kHcBatchSlots);
+    const uint32_t att = hc_attempts(level);
+    const int lv = level > 12 ? 12 : level;
+    const int32_t tl = lv == 10 ? 64 : lv == 11 ? 128 : kOptNum, fu = lv == 12 ? 1 : 0;   // as launch_encode_hc
+    const uint64_t slotBytes = hc_batch_slot_bytes(maxChunk, level), tableAt = hc_batch_delta_bytes(maxChunk);
+    for (uint32_t o = 0; o < nChunks;) {
+        const uint32_t g = std::min(nChunks - o, slots);
+        const uint32_t* caps = dstCaps ? dstCaps + o : nullptr;
+        hipLaunchKernelGGL(k_hc_prev_batch_dict, dim3(g), dim3(kPrevThreads), 0, st, srcPtrs + o, srcSizes + o,
+                           maxChunk, dstPtrs + o, ws, slotBytes, state, E);
+        if (lv >= 10)
+            hipLaunchKernelGGL(k_encode_hc_opt_batch_dict, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o,
+                               maxChunk, dstPtrs + o, caps, outSizes + o, ws, slotBytes, tableAt, att, tl, fu, dictEnd,
+                               E, state);
+        else
+            hipLaunchKernelGGL(k_encode_hc_batch_dict, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, maxChunk,
+                               dstPtrs + o, caps, outSizes + o, (const uint8_t*)ws, slotBytes, att, dictEnd, E, state);
         if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
         o += g;
     }

@@ -6,7 +6,7 @@ kernels on the same bytes at -B4 and -B6 (-Sx, no block checksum) as the
 yardstick: the 64 KiB and 1 MiB batch kernels run the same window code on
 the same blocks.  Prints one JSON line.
 
-    python tools/batch_bench.py [--gib 1] [--reps 10] [--level L] [--dict-kib K]
+    python tools/batch_bench.py [--gib 1] [--reps 10] [--level L] [--dict-kib K] [--rows 4KiB,64KiB]
 
 --level L times lz4mtHipCompressBatchEx at that level instead (L >= 3:
 LZ4-HC, its workspace of the full lz4mtHipCompressBatchWorkspaceSize unless
@@ -21,6 +21,14 @@ dictionary of K KiB, the last K KiB of the same App. F input in a tensor of
 its own.  The yardstick is then the plain batch call on the same chunks in
 the same run: every row carries both times, both compression ratios and
 their quotients, and the frame rows are left out.
+
+--level L with --dict-kib K (L >= 3) times lz4mtHipCompressBatchDictHC
+(lz4mtHipDictPrepareHC on its own).  Two yardsticks in every row: the plain
+lz4mtHipCompressBatchEx call at the same level on the same chunks for the
+time ("plain_*"), and the fast dictionary call lz4mtHipCompressBatchDict with
+the same dictionary for the ratio ("fast_dict_*").
+
+--rows picks the chunkings to run (4KiB, 64KiB, 1MiB, ragged; default all).
 
 Capacities are the default (d_dstCaps = NULL: the bound of each size), the
 frame encoder's are the block size; every configuration is decoded back and
@@ -112,13 +120,27 @@ def batch_row(name, src, sizes, reps, level=0, slots=0, dct=None):
     cbytes = int(csz.sum().item())
     gib = total / 2**30
     if dct is not None:
-        dictionary, state = dct
+        dictionary, state, state_hc = dct
 
-        def enc_d():
+        def enc_f():
             r = L.lib.lz4mtHipCompressBatchDict(P(sp.data_ptr()), P(sz.data_ptr()), max_chunk, n, P(cp.data_ptr()),
                                                 None, P(csz.data_ptr()), P(dictionary.data_ptr()), dictionary.numel(),
                                                 P(state.data_ptr()), st)
             assert r == 0, r
+
+        def enc_hc():
+            r = L.lib.lz4mtHipCompressBatchDictHC(P(sp.data_ptr()), P(sz.data_ptr()), max_chunk, n, P(cp.data_ptr()),
+                                                  None, P(csz.data_ptr()), P(dictionary.data_ptr()),
+                                                  dictionary.numel(), P(state_hc.data_ptr()), level,
+                                                  P(ws.data_ptr()), ws.numel(), st)
+            assert r == 0, r
+
+        enc_d = enc_hc if level >= 3 else enc_f
+        fast = {}
+        if level >= 3:   # the ratio's yardstick: the fast codec with the same dictionary
+            ef = timed(enc_f, reps)
+            fast = {"fast_dict_ratio": round(total / int(csz.sum().item()), 4), "fast_dict_compress_ms": round(ef[0], 3),
+                    "fast_dict_compress_ms_min_max": [round(ef[1], 3), round(ef[2], 3)]}
 
         def dec_d():
             r = L.lib.lz4mtHipDecompressBatchDict(P(cp.data_ptr()), P(csz.data_ptr()), n, P(bp.data_ptr()),
@@ -131,9 +153,13 @@ def batch_row(name, src, sizes, reps, level=0, slots=0, dct=None):
         dd = timed(dec_d, reps)
         round_trip()
         dbytes = int(csz.sum().item())
+        kernel, plain = "k_encode_batch_dict", "k_encode_batch16" if max_chunk < 65547 else "k_encode_batch"
+        if level >= 3:
+            kernel = "k_hc_prev_batch_dict + " + ("k_encode_hc_opt_batch_dict" if level >= 10 else "k_encode_hc_batch_dict")
+            plain = "k_hc_prev_batch + " + ("k_encode_hc_opt_batch" if level >= 10 else "k_encode_hc_batch")
+            fast.update({"slots": nslots, "rounds": -(-n // nslots), "workspace_bytes": ws.numel()})
         return {"name": name, "chunks": n, "bytes": total, "max_chunk": max_chunk,
-                "kernel": "k_encode_batch_dict / k_decode_batch_dict",
-                "plain_kernel": "k_encode_batch16" if max_chunk < 65547 else "k_encode_batch",
+                "kernel": kernel + " / k_decode_batch_dict", "plain_kernel": plain, **fast,
                 "ratio": round(total / dbytes, 4), "plain_ratio": round(total / cbytes, 4),
                 "compress_ms": round(ed[0], 3), "compress_ms_min_max": [round(ed[1], 3), round(ed[2], 3)],
                 "compress_gib_s": round(gib / (ed[0] / 1e3), 2),
@@ -192,9 +218,11 @@ def main():
     ap.add_argument("--level", type=int, default=0, help="compression level of the batch and the frame calls")
     ap.add_argument("--slots", type=int, default=0, help="level >= 3: cap the workspace at this many slots")
     ap.add_argument("--dict-kib", type=int, default=0, help="time the dictionary calls with a dictionary of K KiB")
+    ap.add_argument("--rows", default="4KiB,64KiB,1MiB,ragged", help="chunkings to run")
     a = ap.parse_args()
-    if a.dict_kib and a.level >= 3:
-        sys.exit("--dict-kib times the fast codec: no --level")
+    want = set(a.rows.split(","))
+    if not want <= {"4KiB", "64KiB", "1MiB", "ragged"}:
+        sys.exit("--rows: a comma-separated subset of 4KiB,64KiB,1MiB,ragged")
     if not torch.cuda.is_available():
         sys.exit("batch_bench.py needs a HIP device")
     n = int(a.gib * 2**30) & ~((1 << 20) - 1)
@@ -211,21 +239,38 @@ def main():
             assert r == 0, r
 
         pm = timed(prepare, a.reps)
-        dct = (dictionary, state)
+        state_hc = None
         prep = {"dict_bytes": dictionary.numel(), "dict": "the input's last bytes", "state_bytes": state.numel(),
                 "prepare_ms": round(pm[0], 4), "prepare_ms_min_max": [round(pm[1], 4), round(pm[2], 4)]}
+        if a.level >= 3:
+            state_hc = torch.empty(L.lib.lz4mtHipDictStateSizeHC(), dtype=torch.uint8, device="cuda")
+
+            def prepare_hc():
+                r = L.lib.lz4mtHipDictPrepareHC(P(dictionary.data_ptr()), dictionary.numel(), P(state_hc.data_ptr()),
+                                                state_hc.numel(), st)
+                assert r == 0, r
+
+            ph = timed(prepare_hc, a.reps)
+            prep.update({"fast_state_bytes": state.numel(), "fast_prepare_ms": prep["prepare_ms"],
+                         "state_bytes": state_hc.numel(), "prepare_ms": round(ph[0], 4),
+                         "prepare_ms_min_max": [round(ph[1], 4), round(ph[2], 4)]})
+        dct = (dictionary, state, state_hc)
     rows = []
     for name, k in (("4KiB", 4 << 10), ("64KiB", 64 << 10), ("1MiB", 1 << 20)):
-        rows.append(batch_row(name, src, np.full(n // k, k, dtype=np.int64), a.reps, a.level, a.slots, dct))
+        if name in want:
+            rows.append(batch_row(name, src, np.full(n // k, k, dtype=np.int64), a.reps, a.level, a.slots, dct))
     rs = np.random.RandomState(7)
     sizes = rs.randint(1 << 10, (256 << 10) + 1, size=2 * n // (128 << 10) + 16).astype(np.int64)
     sizes = sizes[:int(np.searchsorted(np.cumsum(sizes), n, side="right"))]
-    rows.append(batch_row("ragged 1KiB-256KiB", src, sizes, a.reps, a.level, a.slots, dct))
+    if "ragged" in want:
+        rows.append(batch_row("ragged 1KiB-256KiB", src, sizes, a.reps, a.level, a.slots, dct))
     if dct is not None:   # the yardstick is the plain batch call, in every row
         print(json.dumps({"tool": "batch_bench", "device": torch.cuda.get_device_name(0),
-                          "input": "gen_synthetic seed 42", "bytes": n, "level": 0, "reps": a.reps, "warmup": 2,
-                          "stat": "median", **prep, "batch": rows}))
+                          "input": "gen_synthetic seed 42", "bytes": n, "level": a.level if a.level >= 3 else 0,
+                          "reps": a.reps, "warmup": 2, "stat": "median", **prep, "batch": rows}))
         return
+    if not {"64KiB", "1MiB"} <= want:
+        sys.exit("the frame yardstick needs the 64KiB and 1MiB rows")
     frames = [frame_row(src, 4, a.reps, a.level), frame_row(src, 6, a.reps, a.level)]
     by = {r["name"]: r for r in rows}
     gaps = {}
