@@ -796,7 +796,11 @@ int orc_frame_decompress(const uint8_t* src, size_t n, uint8_t* dst, size_t outC
                of this frame's output so far */
             /* the blocks read before a read error are still decoded and
                written (the reference handles each block as it is read); a
-               block's own failure comes first in stream order */
+               block's own failure comes first in stream order: the reference
+               quits there and never reads the later size word, data or
+               checksum word that the scan above stopped on (so does R_ERROR
+               for a block that does not fit outCap, which cannot happen at
+               the contract's capacity of one blockMax slot per block) */
             uint8_t* hist = (uint8_t*)calloc(65536 + bm, 1);
             size_t w = frameOut;
             int bres = R_OK;
@@ -814,7 +818,7 @@ int orc_frame_decompress(const uint8_t* src, size_t n, uint8_t* dst, size_t outC
                 memcpy(dst + w, hist + 65536, (size_t)d);
                 w += (size_t)d;
             }
-            if (bres != R_OK && (result == R_OK || result == R_ERROR)) result = bres;
+            if (bres != R_OK) result = bres;
             free(hist);
             free(jobs);
             out = w;

@@ -61,7 +61,11 @@ def lsic(n):
     return bytes(out)
 
 
-class _Writer:
+class Writer:
+    """One block under construction: ``seq`` per sequence, ``finish`` for the last literals.
+    ``matches`` lists every match as (output position, offset, length) for callers that
+    classify sources themselves (lz4_frame_synth.py)."""
+
     def __init__(self, rnd, hist):
         self.rnd = rnd
         self.hist = bytes(hist)
@@ -71,6 +75,7 @@ class _Writer:
         self.stats = collections.Counter()
         self.last_mlen = MFLIMIT
         self.valid = True
+        self.matches = []
 
     @property
     def op(self):
@@ -89,6 +94,7 @@ class _Writer:
         if mlen - MINMATCH >= 15:
             self.block += lsic(mlen - MINMATCH - 15)
         src = self.op - off
+        self.matches.append((self.op, off, mlen))
         hist, H, plain = self.hist, self.H, self.plain
         for s in range(src, src + mlen):      # byte by byte: an overlapping match reads what it wrote
             if s >= 0:
@@ -101,9 +107,12 @@ class _Writer:
         self.last_mlen = mlen
         self.stats["sequences"] += 1
 
-    def finish(self):
-        """The last sequence: literals only, at least 5, and the last match at or before n - 12."""
-        lit = max(LASTLITERALS, MFLIMIT - self.last_mlen) + self.rnd.choice((0, 0, 1, 9, 10, 11, 40, 300))
+    def finish(self, lit=None):
+        """The last sequence: literals only, at least 5, and the last match at or before n - 12
+        (``lit``: exactly that many, for a block of a chosen size)."""
+        if lit is None:
+            lit = max(LASTLITERALS, MFLIMIT - self.last_mlen) + self.rnd.choice((0, 0, 1, 9, 10, 11, 40, 300))
+        assert lit >= max(LASTLITERALS, MFLIMIT - self.last_mlen) or not self.matches
         lits = self.rnd.randbytes(lit)
         self.block.append(min(lit, 15) << 4)
         if lit >= 15:
@@ -111,6 +120,9 @@ class _Writer:
         self.block += lits
         self.plain += lits
         return bytes(self.block), bytes(self.plain), self.stats
+
+
+_Writer = Writer
 
 
 def _count(w, lit, mlen, off_class=None, dict_class=None, p=None, far=False):
@@ -222,7 +234,8 @@ def _dict_seq(w, lit, mlen, cls):
     return True
 
 
-def _mixed_seq(w, room):
+def mixed_seq(w, room):
+    """One sequence of the "mixed" kind: literal run, match length and source class at random."""
     rnd = w.rnd
     lit, mlen = _pick_lit(rnd), _pick_mlen(rnd, room)
     if w.H and rnd.random() < 0.3 and _dict_seq(w, lit, mlen, rnd.choice(DICT_CLASSES[:-2])):
@@ -235,11 +248,14 @@ def _mixed_seq(w, room):
             w.seq(lit, 1, mlen)
 
 
-def _grow(w, upto):
+def grow(w, upto):
     """Cheap bulk up to output position ``upto``: long matches close behind."""
     while w.op < upto:
         lit = w.rnd.randrange(20, 300)
         w.seq(lit, w.rnd.randrange(1, lit + 1), min(upto - w.op, w.rnd.randrange(1500, 4000)) + MINMATCH)
+
+
+_mixed_seq, _grow = mixed_seq, grow      # the names older callers use
 
 
 def _run_far(w):
@@ -277,7 +293,7 @@ def _run_cross(w):
     w.stats[("run", "cross4096")] += 1
 
 
-def synth(rnd, hist, n_target, profile="mixed"):
+def synth(rnd, hist, n_target, profile="mixed", writer=None):
     """(block, plain, stats): an LZ4 block of about ``n_target`` decoded bytes against dictionary ``hist``.
 
     ``profile`` is a kind or a dict {"kind": ..., "low": c, "high": c}:
@@ -289,10 +305,13 @@ def synth(rnd, hist, n_target, profile="mixed"):
     "low" / "high" ask for one dictionary class at P < 64 (the block's first sequence) and at the
     first P in [16384, 60000]; stats[("forced", ...)] says whether it fitted.  Valid blocks keep
     lz4's end-of-block rules, so the expected output of a valid block is ``plain`` for any decoder.
+    ``writer``: a list that receives the Writer (its ``matches``) of the block.
     """
     p = {"kind": profile} if isinstance(profile, str) else dict(profile)
     kind, low, high = p.get("kind", "mixed"), p.get("low"), p.get("high")
-    w = _Writer(rnd, hist)
+    w = Writer(rnd, hist)
+    if writer is not None:
+        writer.append(w)
     bad_at = rnd.randrange(0, max(n_target - 40, 1)) if kind == "invalid" else None
     if low:
         # "first_byte" of a 65 535-byte dictionary is reachable from P = 0 only
@@ -318,19 +337,19 @@ def synth(rnd, hist, n_target, profile="mixed"):
         if kind == "runs":
             c = rnd.randrange(4)
             if c == 0 and (w.op >= 16400 or room > 17000):
-                _grow(w, max(w.op, 16400 + rnd.randrange(0, 3000)))
+                grow(w, max(w.op, 16400 + rnd.randrange(0, 3000)))
                 _run_far(w)
             elif c == 1:
                 _run_dict(w)
             elif c == 2:
                 if w.op < 100:
-                    _grow(w, 100)
+                    grow(w, 100)
                 _run_cross(w)
             else:
                 for _ in range(rnd.randrange(1, 12)):
-                    _mixed_seq(w, room)
+                    mixed_seq(w, room)
         else:
-            _mixed_seq(w, room)
+            mixed_seq(w, room)
     block, plain, stats = w.finish()
     if kind == "invalid":
         assert stats["invalid"] == 1 and not w.valid
