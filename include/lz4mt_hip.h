@@ -420,6 +420,75 @@ Lz4MtResult lz4mtHipCompressBatchDictHC(const void* const* d_srcPtrs, const uint
                                         uint32_t dictSize, const void* d_stateHC, int level, void* d_workspace,
                                         uint64_t workspaceSize, void* stream);
 
+/* ---- 5d. a set of dictionaries, one index per chunk -------------------------
+ * The operators of section 5b for a batch whose chunks belong to many
+ * dictionaries (one per table, column, tenant, message type): one call, one
+ * launch, whatever the number of dictionaries.  Dictionary k is
+ * d_dictPtrs[k] [0, d_dictSizes[k]), at any alignment; it may end on the
+ * last byte of its allocation, and the same dictionary may be listed more
+ * than once.  Chunk i uses dictionary d_chunkDict[i], or none when that is
+ * LZ4MT_HIP_BATCH_NO_DICT.  d_dictPtrs, d_dictSizes and d_chunkDict are
+ * device arrays like the others and the host reads none of them: all three
+ * calls allocate nothing, synchronise nothing and are graph-capturable
+ * exactly as section 5b's.  The effective size of a dictionary (0 below 8
+ * bytes, else min(size, LZ4MT_HIP_DICT_WINDOW)) and its end (pointer + size,
+ * in 64-bit arithmetic) are computed on the device.
+ *
+ * States: state k stands at d_states + k * lz4mtHipDictStateSize(); d_states
+ * is 256-byte aligned and statesSize >= nDicts * lz4mtHipDictStateSize().
+ * lz4mtHipDictSetPrepare builds them all with one launch.  State k is byte
+ * for byte what lz4mtHipDictPrepare writes for dictionary k, and a state made
+ * by either call is valid for the other.  A dictionary with a null pointer
+ * and an effective size above 0 gets a state that no dictionary matches: the
+ * compress call refuses its chunks.
+ *
+ * Compress: a chunk with k = d_chunkDict[i] < nDicts gets the bytes and
+ * d_outSizes[i] of lz4mtHipCompressBatchDict called with dictionary k and
+ * state k.  k == LZ4MT_HIP_BATCH_NO_DICT is the same without a dictionary
+ * (section 5b with dictSize = 0: a fresh lz4 stream, byU32) and needs no
+ * state.  LZ4MT_HIP_BATCH_BAD_CHUNK and nothing written, decided on the
+ * device and with no effect on any other chunk of the call: the chunks
+ * lz4mtHipCompressBatch refuses; an index >= nDicts other than
+ * LZ4MT_HIP_BATCH_NO_DICT; a dictionary with a null pointer and a size above
+ * 0; a state whose recorded size differs from the dictionary's effective
+ * size (section 5b's stale-state guard, per chunk).  d_dstCaps == NULL,
+ * maxChunkBytes and the memory contract are those of lz4mtHipCompressBatch.
+ *
+ * Decompress: chunk i is LZ4_decompress_safe_usingDict against the whole of
+ * dictionary k, every negative return included; with
+ * LZ4MT_HIP_BATCH_NO_DICT or a dictionary of size 0 it is
+ * LZ4_decompress_safe (lz4mtHipDecompressBatch).  LZ4MT_HIP_BATCH_BAD_CHUNK
+ * for an index that names no dictionary or a dictionary with a null pointer
+ * and a size above 0, and for the chunks lz4mtHipDecompressBatch refuses.  It
+ * needs no states, and decodes LZ4-HC blocks as section 5b's decoder does.
+ *
+ * LZ4-HC *compress* with a set of dictionaries is not part of this section:
+ * its state is some 256 KiB per dictionary and its kernels are section 5c's.
+ * Until that follow-up, lz4mtHipCompressBatchDictHC is called once per
+ * dictionary; the blocks it makes are decoded by the call below.
+ *
+ * LZ4MT_RESULT_BAD_ARG, in this order: a null chunk array with nChunks > 0
+ * (d_chunkDict counts as one; d_dstCaps may be null for compress only);
+ * maxChunkBytes above the maximum; a null d_dictPtrs or d_dictSizes with
+ * nDicts > 0; (prepare, compress, with nDicts > 0) d_states null or not
+ * 256-byte aligned, (prepare) or statesSize too small.  Then
+ * LZ4MT_RESULT_ERROR without a HIP device or on a launch error; else
+ * LZ4MT_RESULT_OK.  nDicts == 0 is valid (every chunk must then name
+ * LZ4MT_HIP_BATCH_NO_DICT); nChunks == 0, or nDicts == 0 in prepare,
+ * launches nothing. */
+#define LZ4MT_HIP_BATCH_NO_DICT UINT32_MAX
+Lz4MtResult lz4mtHipDictSetPrepare(const void* const* d_dictPtrs, const uint32_t* d_dictSizes, uint32_t nDicts,
+                                   void* d_states, uint64_t statesSize, void* stream);
+Lz4MtResult lz4mtHipCompressBatchDictSet(const void* const* d_srcPtrs, const uint32_t* d_srcSizes,
+                                         uint32_t maxChunkBytes, uint32_t nChunks, void* const* d_dstPtrs,
+                                         const uint32_t* d_dstCaps, int32_t* d_outSizes,
+                                         const void* const* d_dictPtrs, const uint32_t* d_dictSizes, uint32_t nDicts,
+                                         const void* d_states, const uint32_t* d_chunkDict, void* stream);
+Lz4MtResult lz4mtHipDecompressBatchDictSet(const void* const* d_srcPtrs, const uint32_t* d_srcSizes, uint32_t nChunks,
+                                           void* const* d_dstPtrs, const uint32_t* d_dstCaps, int32_t* d_outSizes,
+                                           const void* const* d_dictPtrs, const uint32_t* d_dictSizes, uint32_t nDicts,
+                                           const uint32_t* d_chunkDict, void* stream);
+
 /* ---- 6. diagnostics ----------------------------------------------------- */
 /* Runs s_memtime-stamped twins of the encode / decode kernels (never the
  * product launch) and sums per-phase shader cycles over all blocks.

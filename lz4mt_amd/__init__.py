@@ -31,6 +31,7 @@ __all__ = [
     "batch_compress_workspace", "BATCH_HC_SLOTS",
     "DICT_WINDOW", "PreparedDict", "prepare_dict", "compress_batch_dict", "decompress_batch_dict",
     "prepare_dict_hc", "compress_batch_dict_hc", "batch_compress_dict_workspace",
+    "BATCH_NO_DICT", "PreparedDictSet", "prepare_dict_set", "compress_batch_dict_set", "decompress_batch_dict_set",
 ]
 
 lib = _abi.load()
@@ -440,6 +441,150 @@ def decompress_batch_dict(blocks, caps, dictionary, stream=None):
     if len(caps) != len(blocks) or any(c < 0 or c >= 1 << 31 for c in caps):
         raise ValueError("caps: one capacity of 0 .. 2^31 - 1 per block")
     return _batch("lz4mtHipDecompressBatchDict", blocks, caps, False, None, stream, dict_args=_dict_ptr(dictionary))
+
+
+# a set of dictionaries and an index per chunk (lz4mt_hip.h section 5d)
+BATCH_NO_DICT = _abi.BATCH_NO_DICT
+
+
+class PreparedDictSet:
+    """A set of dictionaries ready for compress_batch_dict_set:
+    ``dictionaries`` (the caller's uint8 device tensors, kept alive here),
+    ``ptrs`` (int64) and ``sizes`` (int32, u32 bit patterns): the device
+    arrays lz4mtHipDictSetPrepare read, and ``states``: a uint8 device tensor
+    of ``len(dictionaries)`` states of lz4mtHipDictStateSize bytes each, or
+    None when the set was built for decoding only."""
+    __slots__ = ("dictionaries", "ptrs", "sizes", "states")
+
+    def __init__(self, dictionaries, ptrs, sizes, states):
+        self.dictionaries = dictionaries
+        self.ptrs = ptrs
+        self.sizes = sizes
+        self.states = states
+
+    def __len__(self):
+        return len(self.dictionaries)
+
+
+def _torch_stream(stream, dev):
+    if stream is None:
+        return torch.cuda.current_stream(dev)
+    if isinstance(stream, torch.cuda.Stream):
+        return stream
+    return torch.cuda.ExternalStream(int(stream), device=dev)
+
+
+def _dict_set(dictionaries, stream, states):
+    """The device arrays of a set (uploaded on ``stream`` from pinned memory,
+    no synchronisation) and, with ``states``, lz4mtHipDictSetPrepare."""
+    dictionaries = list(dictionaries)
+    for i, d in enumerate(dictionaries):
+        _check_dev(d, f"dictionaries[{i}]")
+        if d.numel() >= 1 << 32:
+            raise ValueError("a dictionary is at most 2^32 - 1 bytes")
+    k = len(dictionaries)
+    dev = dictionaries[0].device if k else torch.device("cuda", torch.cuda.current_device())
+    ts = _torch_stream(stream, dev)
+    with torch.cuda.stream(ts):
+        host = torch.empty(max(12 * k, 16), dtype=torch.uint8, pin_memory=True)   # [pointers | sizes]
+        host[:8 * k].view(torch.int64)[:] = torch.tensor([d.data_ptr() if d.numel() else 0 for d in dictionaries],
+                                                         dtype=torch.int64)
+        host[8 * k:12 * k].view(torch.int32)[:] = torch.tensor([d.numel() for d in dictionaries],
+                                                               dtype=torch.int64).to(torch.int32)
+        desc = host.to(dev, non_blocking=True)
+        ptrs, sizes = desc[:8 * k].view(torch.int64), desc[8 * k:12 * k].view(torch.int32)
+        st = None
+        if states:
+            st = torch.empty(k * int(lib.lz4mtHipDictStateSize()), dtype=torch.uint8, device=dev)
+            assert st.data_ptr() % 256 == 0
+            r = lib.lz4mtHipDictSetPrepare(ctypes.c_void_p(ptrs.data_ptr()), ctypes.c_void_p(sizes.data_ptr()), k,
+                                           ctypes.c_void_p(st.data_ptr()), st.numel(),
+                                           ctypes.c_void_p(ts.cuda_stream))
+            if r != Result.OK:
+                raise Lz4MtError(r, "lz4mtHipDictSetPrepare")
+    return PreparedDictSet(dictionaries, ptrs, sizes, st)
+
+
+def prepare_dict_set(dictionaries, stream=None):
+    """lz4mtHipDictSetPrepare: what prepare_dict does, for every tensor of
+    ``dictionaries`` (contiguous uint8 on one HIP device, any size and
+    alignment) with one kernel on ``stream``.  Returns a PreparedDictSet.
+    Does not synchronise."""
+    return _dict_set(dictionaries, stream, True)
+
+
+def _which(which, n, k, dev, ts):
+    """``which`` (an int below ``k`` or None per chunk) as the device array
+    d_chunkDict, uploaded on ``ts``."""
+    which = list(which)
+    if len(which) != n:
+        raise ValueError("which: one entry per chunk")
+    idx = []
+    for w in which:
+        if w is None:
+            idx.append(BATCH_NO_DICT)
+        elif 0 <= int(w) < k:
+            idx.append(int(w))
+        else:
+            raise ValueError(f"which: {w!r} names none of the {k} dictionaries")
+    with torch.cuda.stream(ts):
+        host = torch.empty(max(n, 1), dtype=torch.int32, pin_memory=True)
+        host[:n] = torch.tensor(idx, dtype=torch.int64).to(torch.int32)   # (u32 bit patterns)
+        return host.to(dev, non_blocking=True)
+
+
+def compress_batch_dict_set(chunks, prepared, which, caps=None, stream=None):
+    """lz4mtHipCompressBatchDictSet: compress_batch_dict with a dictionary per
+    chunk, in one launch: chunk ``i`` gets dictionary ``which[i]`` of
+    ``prepared`` (prepare_dict_set), or none when ``which[i]`` is None.
+    Returns ``(outs, sizes)`` as compress_batch does; decode with
+    decompress_batch_dict_set, the same set and the same ``which``.  Does not
+    synchronise: ``chunks`` and ``prepared`` must stay alive until ``stream``
+    has run the call, and ``stream`` must be ordered after the one
+    prepare_dict_set ran on."""
+    if not isinstance(prepared, PreparedDictSet) or prepared.states is None:
+        raise TypeError("prepared must come from prepare_dict_set")
+    chunks = list(chunks)
+    for i, c in enumerate(chunks):
+        _check_dev(c, f"chunks[{i}]")
+    big = max((c.numel() for c in chunks), default=0)
+    if big > BATCH_MAX_CHUNK:
+        raise ValueError(f"a chunk of {big} bytes exceeds the batch maximum of {BATCH_MAX_CHUNK}")
+    null_caps = caps is None
+    if null_caps:
+        caps = [batch_compress_bound(c.numel()) for c in chunks]
+    else:
+        caps = [int(c) for c in caps]
+        if len(caps) != len(chunks) or any(c < 0 or c >= 1 << 32 for c in caps):
+            raise ValueError("caps: one capacity of 0 .. 2^32 - 1 per chunk")
+    dev = chunks[0].device if chunks else prepared.states.device
+    ts = _torch_stream(stream, dev)
+    idx = _which(which, len(chunks), len(prepared), dev, ts)
+    dict_args = (ctypes.c_void_p(prepared.ptrs.data_ptr()), ctypes.c_void_p(prepared.sizes.data_ptr()),
+                 len(prepared), ctypes.c_void_p(prepared.states.data_ptr()), ctypes.c_void_p(idx.data_ptr()))
+    return _batch("lz4mtHipCompressBatchDictSet", chunks, caps, null_caps, big, ts, dict_args=dict_args)
+
+
+def decompress_batch_dict_set(blocks, caps, dictionaries, which, stream=None):
+    """lz4mtHipDecompressBatchDictSet: decompress_batch_dict with a dictionary
+    per block, in one launch.  ``dictionaries``: the PreparedDictSet the
+    blocks were compressed with, or a list of uint8 device tensors;
+    ``which[i]``: the index of block ``i``'s dictionary, or None for a block
+    made without one.  Does not synchronise."""
+    blocks = list(blocks)
+    for i, b in enumerate(blocks):
+        _check_dev(b, f"blocks[{i}]")
+    caps = [int(c) for c in caps]
+    if len(caps) != len(blocks) or any(c < 0 or c >= 1 << 31 for c in caps):
+        raise ValueError("caps: one capacity of 0 .. 2^31 - 1 per block")
+    if not isinstance(dictionaries, PreparedDictSet):
+        dictionaries = _dict_set(dictionaries, stream, False)
+    dev = blocks[0].device if blocks else dictionaries.ptrs.device
+    ts = _torch_stream(stream, dev)
+    idx = _which(which, len(blocks), len(dictionaries), dev, ts)
+    dict_args = (ctypes.c_void_p(dictionaries.ptrs.data_ptr()), ctypes.c_void_p(dictionaries.sizes.data_ptr()),
+                 len(dictionaries), ctypes.c_void_p(idx.data_ptr()))
+    return _batch("lz4mtHipDecompressBatchDictSet", blocks, caps, False, None, ts, dict_args=dict_args)
 
 
 def frame_bound(n, sd=None):

@@ -36,6 +36,7 @@ BATCH_MAX_CHUNK = 4 << 20
 BATCH_BAD_CHUNK = -(1 << 31)
 BATCH_HC_SLOTS = 16384
 DICT_WINDOW = 64 << 10
+BATCH_NO_DICT = 0xFFFFFFFF
 
 
 class Lz4MtFlg(ctypes.Structure):
@@ -111,6 +112,11 @@ PROTOTYPES = {
     "lz4mtHipCompressBatchDictWorkspaceSize": (c_uint64, [c_uint32, c_uint32, c_int]),
     "lz4mtHipCompressBatchDictHC": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p,
                                             c_void_p, c_uint32, c_void_p, c_int, c_void_p, c_uint64, c_void_p]),
+    "lz4mtHipDictSetPrepare": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint64, c_void_p]),
+    "lz4mtHipCompressBatchDictSet": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p]),
+    "lz4mtHipDecompressBatchDictSet": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_uint32, c_void_p, c_void_p]),
     "lz4mtHipFrameBound": (c_uint64, [c_uint64, SD_P]),
     "lz4mtHipCompressWorkspaceSize": (c_uint64, [c_uint64, SD_P]),
     "lz4mtHipCompressFrame": (c_int, [c_void_p, c_uint64, c_void_p, c_uint64, ctypes.POINTER(c_uint64), SD_P,

@@ -34,6 +34,9 @@ constexpr uint32_t kDictStateBytes = 16384 + 256;
 inline uint32_t dict_effective(uint32_t dictSize) {
     return dictSize < kDictHashUnit ? 0u : (dictSize < kDictWindow ? dictSize : kDictWindow);
 }
+// A set of dictionaries with an index per chunk (section 5d): the index of a
+// chunk that has none (LZ4MT_HIP_BATCH_NO_DICT).
+constexpr uint32_t kBatchNoDict = 0xFFFFFFFFu;
 
 #ifdef __HIP__
 // One chunk's descriptor, read at the uniform index blockIdx.x (scalar
@@ -161,6 +164,23 @@ hipError_t launch_encode_batch_dict(const uint8_t* const* srcPtrs, const uint32_
 hipError_t launch_decode_batch_dict(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t nChunks,
                                     uint8_t* const* dstPtrs, const uint32_t* dstCaps, int32_t* outSizes,
                                     const uint8_t* dictEnd, uint32_t dictSize, hipStream_t st);
+// the same with a set of dictionaries and an index per chunk (section 5d;
+// k_dict_set_prepare, k_encode_batch_dict_set, k_decode_batch_dict_set).
+// dictPtrs / dictSizes / chunkDict are device arrays: the kernels compute the
+// dictionary's end and dict_effective themselves.  State k stands at states +
+// k * kDictStateBytes (256-byte aligned) and is what launch_dict_prepare
+// writes for dictionary k.  chunkDict[i] = kBatchNoDict: no dictionary.
+hipError_t launch_dict_set_prepare(const uint8_t* const* dictPtrs, const uint32_t* dictSizes, uint32_t nDicts,
+                                   uint32_t* states, hipStream_t st);
+hipError_t launch_encode_batch_dict_set(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
+                                        uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps,
+                                        int32_t* outSizes, const uint8_t* const* dictPtrs, const uint32_t* dictSizes,
+                                        uint32_t nDicts, const uint32_t* states, const uint32_t* chunkDict,
+                                        hipStream_t st);
+hipError_t launch_decode_batch_dict_set(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t nChunks,
+                                        uint8_t* const* dstPtrs, const uint32_t* dstCaps, int32_t* outSizes,
+                                        const uint8_t* const* dictPtrs, const uint32_t* dictSizes, uint32_t nDicts,
+                                        const uint32_t* chunkDict, hipStream_t st);
 // the serial frame walk fused with the decode (k_decode_walk): records are
 // decoded as the walk publishes them.  ctl: 8 zeroed device words.
 hipError_t launch_decode_walk(const uint8_t* frame, uint64_t frameSize, uint64_t bodyPos, uint32_t blockMax,

@@ -652,6 +652,61 @@ extern "C" Lz4MtResult lz4mtHipDecompressBatchDict(const void* const* d_srcPtrs,
     return LZ4MT_RESULT_OK;
 }
 
+// The same with a set of dictionaries and an index per chunk (section 5d).
+// The dictionaries' pointers and sizes are device arrays the host never
+// reads: trimming, the stale-state guard and the index check are the kernels'.
+static_assert(LZ4MT_HIP_BATCH_NO_DICT == kBatchNoDict, "batch ABI");
+extern "C" Lz4MtResult lz4mtHipDictSetPrepare(const void* const* d_dictPtrs, const uint32_t* d_dictSizes,
+                                              uint32_t nDicts, void* d_states, uint64_t statesSize, void* stream) {
+    if (nDicts && (!d_dictPtrs || !d_dictSizes)) return LZ4MT_RESULT_BAD_ARG;
+    if (nDicts && (!d_states || (reinterpret_cast<uintptr_t>(d_states) & 255) != 0 ||
+                   statesSize < (uint64_t)nDicts * kDictStateBytes))
+        return LZ4MT_RESULT_BAD_ARG;
+    if (!have_device()) return LZ4MT_RESULT_ERROR;
+    if (nDicts == 0) return LZ4MT_RESULT_OK;
+    HIPCHK(launch_dict_set_prepare(reinterpret_cast<const uint8_t* const*>(d_dictPtrs), d_dictSizes, nDicts,
+                                   static_cast<uint32_t*>(d_states), static_cast<hipStream_t>(stream)));
+    return LZ4MT_RESULT_OK;
+}
+
+extern "C" Lz4MtResult lz4mtHipCompressBatchDictSet(const void* const* d_srcPtrs, const uint32_t* d_srcSizes,
+                                                    uint32_t maxChunkBytes, uint32_t nChunks, void* const* d_dstPtrs,
+                                                    const uint32_t* d_dstCaps, int32_t* d_outSizes,
+                                                    const void* const* d_dictPtrs, const uint32_t* d_dictSizes,
+                                                    uint32_t nDicts, const void* d_states,
+                                                    const uint32_t* d_chunkDict, void* stream) {
+    if (nChunks && (!d_srcPtrs || !d_srcSizes || !d_dstPtrs || !d_outSizes || !d_chunkDict))
+        return LZ4MT_RESULT_BAD_ARG;
+    if (maxChunkBytes > LZ4MT_HIP_BATCH_MAX_CHUNK) return LZ4MT_RESULT_BAD_ARG;
+    if (nDicts && (!d_dictPtrs || !d_dictSizes)) return LZ4MT_RESULT_BAD_ARG;
+    if (nDicts && (!d_states || (reinterpret_cast<uintptr_t>(d_states) & 255) != 0)) return LZ4MT_RESULT_BAD_ARG;
+    if (!have_device()) return LZ4MT_RESULT_ERROR;
+    if (nChunks == 0) return LZ4MT_RESULT_OK;
+    HIPCHK(launch_encode_batch_dict_set(reinterpret_cast<const uint8_t* const*>(d_srcPtrs), d_srcSizes, maxChunkBytes,
+                                        nChunks, reinterpret_cast<uint8_t* const*>(d_dstPtrs), d_dstCaps, d_outSizes,
+                                        reinterpret_cast<const uint8_t* const*>(d_dictPtrs), d_dictSizes, nDicts,
+                                        static_cast<const uint32_t*>(d_states), d_chunkDict,
+                                        static_cast<hipStream_t>(stream)));
+    return LZ4MT_RESULT_OK;
+}
+
+extern "C" Lz4MtResult lz4mtHipDecompressBatchDictSet(const void* const* d_srcPtrs, const uint32_t* d_srcSizes,
+                                                      uint32_t nChunks, void* const* d_dstPtrs,
+                                                      const uint32_t* d_dstCaps, int32_t* d_outSizes,
+                                                      const void* const* d_dictPtrs, const uint32_t* d_dictSizes,
+                                                      uint32_t nDicts, const uint32_t* d_chunkDict, void* stream) {
+    if (nChunks && (!d_srcPtrs || !d_srcSizes || !d_dstPtrs || !d_dstCaps || !d_outSizes || !d_chunkDict))
+        return LZ4MT_RESULT_BAD_ARG;
+    if (nDicts && (!d_dictPtrs || !d_dictSizes)) return LZ4MT_RESULT_BAD_ARG;
+    if (!have_device()) return LZ4MT_RESULT_ERROR;
+    if (nChunks == 0) return LZ4MT_RESULT_OK;
+    HIPCHK(launch_decode_batch_dict_set(reinterpret_cast<const uint8_t* const*>(d_srcPtrs), d_srcSizes, nChunks,
+                                        reinterpret_cast<uint8_t* const*>(d_dstPtrs), d_dstCaps, d_outSizes,
+                                        reinterpret_cast<const uint8_t* const*>(d_dictPtrs), d_dictSizes, nDicts,
+                                        d_chunkDict, static_cast<hipStream_t>(stream)));
+    return LZ4MT_RESULT_OK;
+}
+
 // LZ4-HC with a shared dictionary (section 5c).  As above the host only trims
 // the dictionary; the state's kind and recorded size are checked on the device.
 extern "C" uint64_t lz4mtHipDictStateSizeHC(void) { return kHcDictStateBytes; }

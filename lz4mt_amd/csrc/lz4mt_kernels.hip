@@ -1700,6 +1700,114 @@ __global__ void __launch_bounds__(64) k_encode_batch_dict(const uint8_t* const* 
     if (L == 0) outSizes[blockIdx.x] = r;
 }
 
+// ---- the same with a set of dictionaries and an index per chunk
+// (lz4mt_hip.h section 5d).  The dictionaries' pointers and sizes are device
+// arrays, so what the host did for the shared dictionary happens here: the
+// effective size (dict_effective) and the dictionary's end, ptr + size in
+// 64-bit arithmetic.  State k is kDictStateBytes further than state k - 1
+// and byte for byte what k_dict_prepare writes for dictionary k.
+// kDictStateBad: the recorded size (word 4096) of a dictionary that has a
+// size and no pointer.  No effective size equals it, so the encoder's guard
+// refuses the chunks that name such a state.
+constexpr uint32_t kDictStateBad = 0xFFFFFFFFu;
+static_assert(kDictStateBad > kDictWindow, "no effective size");
+__device__ __forceinline__ uint32_t dict_effective_dev(uint32_t dictSize) {
+    return dictSize < kDictHashUnit ? 0u : (dictSize < kDictWindow ? dictSize : kDictWindow);
+}
+
+// k_dict_prepare's work, workgroup k for dictionary k (pointer and size are
+// uniform scalar loads).
+__global__ void __launch_bounds__(1024) k_dict_set_prepare(const uint8_t* const* __restrict__ dictPtrs,
+                                                           const uint32_t* __restrict__ dictSizes,
+                                                           uint32_t* __restrict__ states) {
+    using G = V5Geo<false, false, true>;
+    __shared__ uint32_t Tp[4096];
+    const uint32_t t = threadIdx.x, k = blockIdx.x;
+    const uint32_t size = dictSizes[k];
+    const uint8_t* dp = dictPtrs[k];
+    const uint32_t D = dict_effective_dev(size);
+    const bool bad = !dp && D != 0;
+    g_u32* state = (g_u32*)states + (uint64_t)k * (kDictStateBytes / 4);
+    for (uint32_t i = t; i < 4096; i += 1024) Tp[i] = 0;
+    __syncthreads();
+    if (D >= kDictHashUnit && !bad) {
+        g_cu8* h = gptr(dp) + size - kLinkO0;   // h[p]: the byte at position p, valid for p in [kLinkO0 - D, kLinkO0)
+        const uint32_t lo = kLinkO0 - D;
+        const uint32_t cnt = (D - kDictHashUnit) / 3 + 1;
+        for (uint32_t j = t; j < cnt; j += 1024) {
+            const uint32_t p = lo + 3 * j;
+            uint32_t w0 = 0, b4 = h[p + 4];
+            for (uint32_t q = 0; q < 4; ++q) w0 |= (uint32_t)h[p + q] << (8 * q);
+            const uint32_t hs = lz4_hash<false>(w0, b4);
+            atomicMax(&Tp[hs], (p << G::TB) | G::tag(w0));
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = t; i < kDictStateBytes / 4; i += 1024) {
+        uint32_t v = 0;
+        if (i < 4096) {
+            const uint32_t e = Tp[i];
+            v = (e >> G::TB) | (e << G::PB);
+        } else if (i == 4096) {
+            v = bad ? kDictStateBad : D;
+        }
+        state[i] = v;
+    }
+}
+
+// k_encode_batch_dict with the dictionary chosen per chunk: the wave reads
+// its index, then that dictionary's pointer and size and word 4096 of its
+// state (all uniform), copies that state's table into LDS -- or zeroes the
+// table for kBatchNoDict, which needs no state: a fresh stream -- and runs the
+// same stream step.  Refused, with nothing written: an index that names no
+// dictionary, a dictionary with a size and no pointer, a state recorded for
+// another effective size.  The encoder is an instantiation of its own (DUP),
+// so that k_encode_batch_dict's stays the single call site it is inlined at.
+template <bool XC>
+__global__ void __launch_bounds__(64) k_encode_batch_dict_set(const uint8_t* const* __restrict__ srcPtrs,
+                                                              const uint32_t* __restrict__ srcSizes,
+                                                              uint32_t maxChunk, uint8_t* const* __restrict__ dstPtrs,
+                                                              const uint32_t* __restrict__ dstCaps,
+                                                              int32_t* __restrict__ outSizes,
+                                                              const uint8_t* const* __restrict__ dictPtrs,
+                                                              const uint32_t* __restrict__ dictSizes, uint32_t nDicts,
+                                                              const uint32_t* __restrict__ states,
+                                                              const uint32_t* __restrict__ chunkDict) {
+    ENCODE_LDS
+    (void)S;
+    const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, dstCaps);
+    const uint32_t L = laneid();
+    const uint32_t k = chunkDict[blockIdx.x];
+    int32_t r = kBatchBadChunk;
+    bool ok = !c.bad;
+    uint32_t D = 0;
+    g_cu8* dictEnd = nullptr;
+    if (ok && k != kBatchNoDict) {
+        ok = k < nDicts;
+        if (ok) {
+            const uint32_t size = dictSizes[k];
+            const uint8_t* dp = dictPtrs[k];
+            g_cu32* state = (g_cu32*)states + (uint64_t)k * (kDictStateBytes / 4);
+            D = dict_effective_dev(size);
+            dictEnd = gptr(dp) + size;
+            ok = (dp || size == 0) && state[4096] == D;
+            if (ok) {
+                g_cu4* in = (g_cu4*)state;
+                for (uint32_t i = L; i < 1024; i += 64) ((l_u4*)T)[i] = in[i];
+            }
+        }
+    } else if (ok) {
+        for (uint32_t i = L; i < 1024; i += 64) ((l_u4*)T)[i] = (v4u){0, 0, 0, 0};
+    }
+    if (ok) {
+        WAVE_SYNC();
+        const LinkArgs lk{kLinkO0, kLinkO0 - D, kLinkO0 - D, false};
+        [[clang::always_inline]] r = encode_block_v5<false, false, false, true, false, false, true, XC, true, true>(
+            c.s - kLinkO0, kLinkO0 + c.n, c.d, c.cap, (l_u32*)T, (l_u8*)X, nullptr, lk, nullptr, dictEnd - kLinkO0);
+    }
+    if (L == 0) outSizes[blockIdx.x] = r;
+}
+
 // A block-dependent table entry (position | tag, V5Geo<false, false, true>)
 // in the next block's coordinates: position x -> x - n; positions at or
 // below n (older than the next block's 64 KiB window) -> 0, stale like an
@@ -2201,6 +2309,39 @@ hipError_t launch_encode_batch_dict(const uint8_t* const* srcPtrs, const uint32_
     }
     return hipSuccess;
 }
+
+// The same with a set of dictionaries (section 5d): every array is device
+// memory; state k at states + k * kDictStateBytes, 256-byte aligned.
+hipError_t launch_dict_set_prepare(const uint8_t* const* dictPtrs, const uint32_t* dictSizes, uint32_t nDicts,
+                                   uint32_t* states, hipStream_t st) {
+    for (uint32_t o = 0; o < nDicts;) {
+        const uint32_t g = std::min(nDicts - o, kBatchGrid);
+        hipLaunchKernelGGL(k_dict_set_prepare, dim3(g), dim3(1024), 0, st, dictPtrs + o, dictSizes + o,
+                           states + (uint64_t)o * (kDictStateBytes / 4));
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        o += g;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_encode_batch_dict_set(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
+                                        uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps,
+                                        int32_t* outSizes, const uint8_t* const* dictPtrs, const uint32_t* dictSizes,
+                                        uint32_t nDicts, const uint32_t* states, const uint32_t* chunkDict,
+                                        hipStream_t st) {
+    bool xc = true;
+    if (const hipError_t r = encoder_path(st, &xc); r != hipSuccess) return r;
+    const auto k = xc ? k_encode_batch_dict_set<true> : k_encode_batch_dict_set<false>;
+    for (uint32_t o = 0; o < nChunks;) {
+        const uint32_t g = std::min(nChunks - o, kBatchGrid);
+        hipLaunchKernelGGL(k, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, maxChunk, dstPtrs + o,
+                           dstCaps ? dstCaps + o : nullptr, outSizes + o, dictPtrs, dictSizes, nDicts, states,
+                           chunkDict + o);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        o += g;
+    }
+    return hipSuccess;
+}
 #endif
 
 
@@ -2270,7 +2411,9 @@ template <bool XD> struct DecHist {};
 template <> struct DecHist<true> {
     g_cu8* hist;          // one past the dictionary's last byte
 };
-template <bool ST, bool HG = false, bool XD = false>
+// DUP: no effect on the code; a separate instantiation for a kernel that
+// would otherwise be a second call site of another kernel's decode_block.
+template <bool ST, bool HG = false, bool XD = false, bool DUP = false>
 struct Dec : DecHist<XD> {
     uint64_t* acc;
     uint64_t ts;
@@ -2768,8 +2911,8 @@ struct Dec : DecHist<XD> {
 // (forceExtDict): lz4 takes its short match copies only for a match inside
 // the block (match >= lowPrefix), so a match that starts in the dictionary
 // always passes the end-of-output test of the safe match copy.
-template <bool ST, bool HG, bool XD>
-__device__ int32_t decode_block(Dec<ST, HG, XD>& D, int64_t cap) {
+template <bool ST, bool HG, bool XD, bool DUP>
+__device__ int32_t decode_block(Dec<ST, HG, XD, DUP>& D, int64_t cap) {
     const int64_t iend = D.len, oend = cap;
     const int64_t shortiend = iend - 16, shortoend = oend - 32;
     int64_t ip = 0, op = 0, cpy = 0, match = 0, length = 0, ext = 0;
@@ -3062,6 +3205,70 @@ __global__ void __launch_bounds__(64) k_decode_batch_dict(const uint8_t* const* 
     } else {
         Dec<false, true, true> D;
         D.hist = gptr(dictEnd);
+        D.acc = nullptr;
+        D.ts = 0;
+        D.src = gptr(sp);
+        D.len = (int64_t)len;
+        D.dst = gptr(dp);
+        D.physcap = (int64_t)cap;
+        D.ring = (l_u8*)ring;
+        D.win = (l_u8*)win;
+        D.wlo = INT64_MIN / 4;
+        D.labase = INT64_MIN / 4;
+        D.la = 0;
+        D.flushed = 0;
+        D.completed = 0;
+        D.lowP = -(int32_t)min(dictSize, 65536u);
+        res = decode_block(D, (int64_t)cap);
+        if (res == kDecodeOutputTooSmall) res = -1;
+    }
+    if (laneid() == 0) outSizes[i] = res;
+}
+
+// The same with a set of dictionaries and an index per chunk (lz4mt_hip.h
+// section 5d): the wave reads its index, then that dictionary's pointer and
+// size (uniform), and decodes against the whole of it (its end is ptr + size
+// in 64-bit arithmetic).  kBatchNoDict or a dictionary of size 0: lowP = 0,
+// with which this instantiation takes exactly the decisions of
+// k_decode_batch's -- `match >= (XD ? 0 : lowP)` is the same test, every
+// offset below the block is refused before a copy, and so out8 never sees a
+// position below 0: hist is not read.  Refused besides k_decode_batch's
+// chunks: an index that names no dictionary, a dictionary with a size and no
+// pointer.  An instantiation of its own (DUP), so that k_decode_batch_dict's
+// stays the single call site it is inlined at.
+__global__ void __launch_bounds__(64) k_decode_batch_dict_set(const uint8_t* const* __restrict__ srcPtrs,
+                                                              const uint32_t* __restrict__ srcSizes,
+                                                              uint8_t* const* __restrict__ dstPtrs,
+                                                              const uint32_t* __restrict__ dstCaps,
+                                                              int32_t* __restrict__ outSizes,
+                                                              const uint8_t* const* __restrict__ dictPtrs,
+                                                              const uint32_t* __restrict__ dictSizes, uint32_t nDicts,
+                                                              const uint32_t* __restrict__ chunkDict) {
+    __shared__ __attribute__((aligned(16))) uint8_t ring[kRing];
+    __shared__ __attribute__((aligned(16))) uint8_t win[kWinAlloc];
+    const uint32_t i = blockIdx.x;
+    const uint32_t len = srcSizes[i], cap = dstCaps[i], k = chunkDict[i];
+    const uint8_t* sp = srcPtrs[i];
+    uint8_t* dp = dstPtrs[i];
+    uint32_t dictSize = 0;
+    const uint8_t* dict = nullptr;
+    bool badDict = false;
+    if (k != kBatchNoDict) {
+        badDict = k >= nDicts;
+        if (!badDict) {
+            dictSize = dictSizes[k];
+            dict = dictPtrs[k];
+            badDict = !dict && dictSize != 0;
+        }
+    }
+    int32_t res;
+    if (badDict || !dp || (reinterpret_cast<uintptr_t>(dp) & 15) != 0 || (!sp && len != 0)) {
+        res = kBatchBadChunk;
+    } else if (len > 0x7FFFFFFFu || cap > 0x7FFFFFFFu) {
+        res = -1;
+    } else {
+        Dec<false, true, true, true> D;
+        D.hist = gptr(dict) + dictSize;
         D.acc = nullptr;
         D.ts = 0;
         D.src = gptr(sp);
@@ -3687,6 +3894,21 @@ hipError_t launch_decode_batch_dict(const uint8_t* const* srcPtrs, const uint32_
         const uint32_t g = std::min(nChunks - o, kGrid);
         hipLaunchKernelGGL(k_decode_batch_dict, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, dstPtrs + o,
                            dstCaps + o, outSizes + o, dictEnd, dictSize);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        o += g;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_decode_batch_dict_set(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t nChunks,
+                                        uint8_t* const* dstPtrs, const uint32_t* dstCaps, int32_t* outSizes,
+                                        const uint8_t* const* dictPtrs, const uint32_t* dictSizes, uint32_t nDicts,
+                                        const uint32_t* chunkDict, hipStream_t st) {
+    constexpr uint32_t kGrid = 1u << 30;
+    for (uint32_t o = 0; o < nChunks;) {
+        const uint32_t g = std::min(nChunks - o, kGrid);
+        hipLaunchKernelGGL(k_decode_batch_dict_set, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, dstPtrs + o,
+                           dstCaps + o, outSizes + o, dictPtrs, dictSizes, nDicts, chunkDict + o);
         if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
         o += g;
     }

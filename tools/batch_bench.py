@@ -6,7 +6,7 @@ kernels on the same bytes at -B4 and -B6 (-Sx, no block checksum) as the
 yardstick: the 64 KiB and 1 MiB batch kernels run the same window code on
 the same blocks.  Prints one JSON line.
 
-    python tools/batch_bench.py [--gib 1] [--reps 10] [--level L] [--dict-kib K] [--rows 4KiB,64KiB]
+    python tools/batch_bench.py [--gib 1] [--reps 10] [--level L] [--dict-kib K] [--dicts N] [--rows 4KiB,64KiB]
 
 --level L times lz4mtHipCompressBatchEx at that level instead (L >= 3:
 LZ4-HC, its workspace of the full lz4mtHipCompressBatchWorkspaceSize unless
@@ -27,6 +27,16 @@ their quotients, and the frame rows are left out.
 lz4mtHipCompressBatchEx call at the same level on the same chunks for the
 time ("plain_*"), and the fast dictionary call lz4mtHipCompressBatchDict with
 the same dictionary for the ratio ("fast_dict_*").
+
+--dicts N with --dict-kib K (the fast codec only) also times the calls with a
+set of dictionaries (lz4mtHipCompressBatchDictSet /
+lz4mtHipDecompressBatchDictSet; lz4mtHipDictSetPrepare on its own): N
+dictionaries of K KiB, chunk i using dictionary i % N.  The N dictionaries
+hold the same bytes in N allocations of their own, and so do their N states:
+the set calls then do the shared-dictionary call's work on the same chunks
+(the sizes are compared) and differ from it in the per-chunk loads and in the
+memory the tables and dictionaries are read from.  The yardstick is the
+shared-dictionary call in the same row ("set_*_over_shared").
 
 --rows picks the chunkings to run (4KiB, 64KiB, 1MiB, ragged; default all).
 
@@ -120,7 +130,7 @@ def batch_row(name, src, sizes, reps, level=0, slots=0, dct=None):
     cbytes = int(csz.sum().item())
     gib = total / 2**30
     if dct is not None:
-        dictionary, state, state_hc = dct
+        dictionary, state, state_hc, dset = dct
 
         def enc_f():
             r = L.lib.lz4mtHipCompressBatchDict(P(sp.data_ptr()), P(sz.data_ptr()), max_chunk, n, P(cp.data_ptr()),
@@ -153,13 +163,44 @@ def batch_row(name, src, sizes, reps, level=0, slots=0, dct=None):
         dd = timed(dec_d, reps)
         round_trip()
         dbytes = int(csz.sum().item())
+        sset = {}
+        if dset is not None:   # the same chunks through the set calls, chunk i with dictionary i % N
+            d_ptrs, d_sizes, states, nd = dset
+            which = torch.from_numpy((np.arange(n, dtype=np.int64) % nd).astype(np.int32)).cuda()
+            shared_sizes = csz.clone()
+
+            def enc_s():
+                r = L.lib.lz4mtHipCompressBatchDictSet(P(sp.data_ptr()), P(sz.data_ptr()), max_chunk, n,
+                                                       P(cp.data_ptr()), None, P(csz.data_ptr()), P(d_ptrs.data_ptr()),
+                                                       P(d_sizes.data_ptr()), nd, P(states.data_ptr()),
+                                                       P(which.data_ptr()), st)
+                assert r == 0, r
+
+            def dec_s():
+                r = L.lib.lz4mtHipDecompressBatchDictSet(P(cp.data_ptr()), P(csz.data_ptr()), n, P(bp.data_ptr()),
+                                                         P(sz.data_ptr()), P(dsz.data_ptr()), P(d_ptrs.data_ptr()),
+                                                         P(d_sizes.data_ptr()), nd, P(which.data_ptr()), st)
+                assert r == 0, r
+
+            csz.zero_()
+            back.zero_()
+            es = timed(enc_s, reps)
+            dz = timed(dec_s, reps)
+            assert torch.equal(csz, shared_sizes), name   # the same dictionary bytes: the same blocks
+            round_trip()
+            sset = {"dicts": nd, "set_kernel": "k_encode_batch_dict_set / k_decode_batch_dict_set",
+                    "set_compress_ms": round(es[0], 3), "set_compress_ms_min_max": [round(es[1], 3), round(es[2], 3)],
+                    "set_decompress_ms": round(dz[0], 3),
+                    "set_decompress_ms_min_max": [round(dz[1], 3), round(dz[2], 3)],
+                    "set_compress_over_shared": round(es[0] / ed[0], 4),
+                    "set_decompress_over_shared": round(dz[0] / dd[0], 4)}
         kernel, plain = "k_encode_batch_dict", "k_encode_batch16" if max_chunk < 65547 else "k_encode_batch"
         if level >= 3:
             kernel = "k_hc_prev_batch_dict + " + ("k_encode_hc_opt_batch_dict" if level >= 10 else "k_encode_hc_batch_dict")
             plain = "k_hc_prev_batch + " + ("k_encode_hc_opt_batch" if level >= 10 else "k_encode_hc_batch")
             fast.update({"slots": nslots, "rounds": -(-n // nslots), "workspace_bytes": ws.numel()})
         return {"name": name, "chunks": n, "bytes": total, "max_chunk": max_chunk,
-                "kernel": kernel + " / k_decode_batch_dict", "plain_kernel": plain, **fast,
+                "kernel": kernel + " / k_decode_batch_dict", "plain_kernel": plain, **fast, **sset,
                 "ratio": round(total / dbytes, 4), "plain_ratio": round(total / cbytes, 4),
                 "compress_ms": round(ed[0], 3), "compress_ms_min_max": [round(ed[1], 3), round(ed[2], 3)],
                 "compress_gib_s": round(gib / (ed[0] / 1e3), 2),
@@ -218,11 +259,15 @@ def main():
     ap.add_argument("--level", type=int, default=0, help="compression level of the batch and the frame calls")
     ap.add_argument("--slots", type=int, default=0, help="level >= 3: cap the workspace at this many slots")
     ap.add_argument("--dict-kib", type=int, default=0, help="time the dictionary calls with a dictionary of K KiB")
+    ap.add_argument("--dicts", type=int, default=0,
+                    help="with --dict-kib: also time the set calls with N dictionaries, chunk i using i %% N")
     ap.add_argument("--rows", default="4KiB,64KiB,1MiB,ragged", help="chunkings to run")
     a = ap.parse_args()
     want = set(a.rows.split(","))
     if not want <= {"4KiB", "64KiB", "1MiB", "ragged"}:
         sys.exit("--rows: a comma-separated subset of 4KiB,64KiB,1MiB,ragged")
+    if a.dicts and (not a.dict_kib or a.level >= 3 or a.dicts < 0):
+        sys.exit("--dicts: a count of dictionaries, with --dict-kib and the fast codec")
     if not torch.cuda.is_available():
         sys.exit("batch_bench.py needs a HIP device")
     n = int(a.gib * 2**30) & ~((1 << 20) - 1)
@@ -254,7 +299,24 @@ def main():
             prep.update({"fast_state_bytes": state.numel(), "fast_prepare_ms": prep["prepare_ms"],
                          "state_bytes": state_hc.numel(), "prepare_ms": round(ph[0], 4),
                          "prepare_ms_min_max": [round(ph[1], 4), round(ph[2], 4)]})
-        dct = (dictionary, state, state_hc)
+        dset = None
+        if a.dicts:   # N allocations of the same bytes (alive until main returns), N states
+            copies =[dictionary.clone() for _ in range(a.dicts)]
+            d_ptrs = torch.tensor([c.data_ptr() for c in copies], dtype=torch.int64, device="cuda")
+            d_sizes = torch.tensor([c.numel() for c in copies], dtype=torch.int32, device="cuda")
+            states = torch.empty(a.dicts * state.numel(), dtype=torch.uint8, device="cuda")
+
+            def prepare_set():
+                r = L.lib.lz4mtHipDictSetPrepare(P(d_ptrs.data_ptr()), P(d_sizes.data_ptr()), a.dicts,
+                                                 P(states.data_ptr()), states.numel(), st)
+                assert r == 0, r
+
+            ps = timed(prepare_set, a.reps)
+            assert torch.equal(states.view(a.dicts, -1), state.view(1, -1).expand(a.dicts, -1))
+            prep.update({"dicts": a.dicts, "set_states_bytes": states.numel(),
+                         "set_prepare_ms": round(ps[0], 4), "set_prepare_ms_min_max": [round(ps[1], 4), round(ps[2], 4)]})
+            dset = (d_ptrs, d_sizes, states, a.dicts)
+        dct = (dictionary, state, state_hc, dset)
     rows = []
     for name, k in (("4KiB", 4 << 10), ("64KiB", 64 << 10), ("1MiB", 1 << 20)):
         if name in want:
