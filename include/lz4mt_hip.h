@@ -464,8 +464,9 @@ Lz4MtResult lz4mtHipCompressBatchDictHC(const void* const* d_srcPtrs, const uint
  *
  * LZ4-HC *compress* with a set of dictionaries is not part of this section:
  * its state is some 256 KiB per dictionary and its kernels are section 5c's.
- * Until that follow-up, lz4mtHipCompressBatchDictHC is called once per
- * dictionary; the blocks it makes are decoded by the call below.
+ * It is the follow-up of section 5e (lz4mtHipCompressBatchDictSetHC), which
+ * replaces one lz4mtHipCompressBatchDictHC call per dictionary; the blocks
+ * either makes are decoded by the call below.
  *
  * LZ4MT_RESULT_BAD_ARG, in this order: a null chunk array with nChunks > 0
  * (d_chunkDict counts as one; d_dstCaps may be null for compress only);
@@ -488,6 +489,66 @@ Lz4MtResult lz4mtHipDecompressBatchDictSet(const void* const* d_srcPtrs, const u
                                            void* const* d_dstPtrs, const uint32_t* d_dstCaps, int32_t* d_outSizes,
                                            const void* const* d_dictPtrs, const uint32_t* d_dictSizes, uint32_t nDicts,
                                            const uint32_t* d_chunkDict, void* stream);
+
+/* ---- 5e. LZ4-HC (levels 3..12) with a set of dictionaries -------------------
+ * Section 5c's compressor behind section 5d's set: one call for a batch whose
+ * chunks belong to many dictionaries, two launches per round whatever their
+ * number.  d_dictPtrs, d_dictSizes and d_chunkDict are as in section 5d:
+ * device arrays the host never reads, dictionary k at any alignment and free
+ * to end on the last byte of its allocation, the same dictionary listed as
+ * often as wanted, LZ4MT_HIP_BATCH_NO_DICT for a chunk without one.  Both
+ * calls are asynchronous, allocate nothing, synchronise nothing, read no
+ * environment variable and are graph-capturable.  The effective size of a
+ * dictionary is min(size, LZ4MT_HIP_DICT_WINDOW) -- lz4hc's rule: there is no
+ * 8-byte minimum here, and a size below 4 inserts nothing -- and its end is
+ * pointer + size in 64-bit arithmetic; both are computed on the device.
+ *
+ * States: state k stands at d_statesHC + k * lz4mtHipDictStateSizeHC();
+ * d_statesHC is 256-byte aligned and statesSize >= nDicts *
+ * lz4mtHipDictStateSizeHC() (a 64-bit product).  lz4mtHipDictSetPrepareHC
+ * builds them with one workgroup per dictionary, in a bounded number of
+ * launches whatever nDicts is.  State k is byte for byte what
+ * lz4mtHipDictPrepareHC writes for dictionary k, and a state made by either
+ * call serves the other.  A dictionary with a null pointer and a size above 0
+ * gets a state that no dictionary matches; a null pointer with size 0 is a
+ * valid empty dictionary.
+ *
+ * Compress: a chunk with k = d_chunkDict[i] < nDicts gets the bytes and
+ * d_outSizes[i] of lz4mtHipCompressBatchDictHC called with dictionary k,
+ * state k and `level`.  k == LZ4MT_HIP_BATCH_NO_DICT gets the bytes of
+ * lz4mtHipCompressBatchEx at `level` and needs no state: nDicts == 0 with
+ * d_statesHC == NULL is valid (every chunk must then name
+ * LZ4MT_HIP_BATCH_NO_DICT).  LZ4MT_HIP_BATCH_BAD_CHUNK and nothing written,
+ * decided on the device, per chunk and with no effect on any other chunk of
+ * the call: the chunks lz4mtHipCompressBatch refuses; an index >= nDicts
+ * other than LZ4MT_HIP_BATCH_NO_DICT; a dictionary with a null pointer and a
+ * size above 0; a state that is not an HC state for that dictionary's
+ * effective size (stale, unprepared, or a state of section 5b / 5d).  Levels,
+ * d_dstCaps == NULL and the memory contract are those of section 5c: no byte
+ * outside a dictionary's effective part, and no byte outside a chunk, is
+ * read.  lz4mtHipDecompressBatchDictSet decodes the blocks.
+ *
+ * Workspace: lz4mtHipCompressBatchDictWorkspaceSize(maxChunkBytes, nChunks,
+ * level), the slots and rounds of section 5c: any 256-byte-aligned workspace
+ * of at least one slot is accepted, and a smaller one costs time, never
+ * bytes.  A round takes its slice of d_chunkDict with the other chunk arrays.
+ *
+ * LZ4MT_RESULT_BAD_ARG, in this order: a null chunk array with nChunks > 0
+ * (d_chunkDict counts as one; d_dstCaps may be null); maxChunkBytes above the
+ * maximum; level < 3; a null d_dictPtrs or d_dictSizes with nDicts > 0; with
+ * nDicts > 0, d_statesHC null or not 256-byte aligned, (prepare) or
+ * statesSize too small; with nChunks > 0 a workspace that is null, not
+ * 256-byte aligned or smaller than one slot.  Then LZ4MT_RESULT_ERROR without
+ * a HIP device or on a launch error; else LZ4MT_RESULT_OK.  nChunks == 0, or
+ * nDicts == 0 in prepare, launches nothing. */
+Lz4MtResult lz4mtHipDictSetPrepareHC(const void* const* d_dictPtrs, const uint32_t* d_dictSizes, uint32_t nDicts,
+                                     void* d_statesHC, uint64_t statesSize, void* stream);
+Lz4MtResult lz4mtHipCompressBatchDictSetHC(const void* const* d_srcPtrs, const uint32_t* d_srcSizes,
+                                           uint32_t maxChunkBytes, uint32_t nChunks, void* const* d_dstPtrs,
+                                           const uint32_t* d_dstCaps, int32_t* d_outSizes,
+                                           const void* const* d_dictPtrs, const uint32_t* d_dictSizes, uint32_t nDicts,
+                                           const void* d_statesHC, const uint32_t* d_chunkDict, int level,
+                                           void* d_workspace, uint64_t workspaceSize, void* stream);
 
 /* ---- 6. diagnostics ----------------------------------------------------- */
 /* Runs s_memtime-stamped twins of the encode / decode kernels (never the

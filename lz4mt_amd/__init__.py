@@ -32,6 +32,7 @@ __all__ = [
     "DICT_WINDOW", "PreparedDict", "prepare_dict", "compress_batch_dict", "decompress_batch_dict",
     "prepare_dict_hc", "compress_batch_dict_hc", "batch_compress_dict_workspace",
     "BATCH_NO_DICT", "PreparedDictSet", "prepare_dict_set", "compress_batch_dict_set", "decompress_batch_dict_set",
+    "prepare_dict_set_hc", "compress_batch_dict_set_hc",
 ]
 
 lib = _abi.load()
@@ -192,7 +193,8 @@ def _batch(fn_name, srcs, caps, null_caps, max_chunk, stream, level=0, workspace
     ``level`` >= 3 (compress only): lz4mtHipCompressBatchEx, its workspace
     allocated here on the call's stream unless one is given.
     ``dict_args`` (the dictionary calls): the arguments between d_outSizes
-    and the stream (with ``level`` >= 3: and the level), as ctypes values."""
+    and the stream (with ``level`` >= 3: and the level), as ctypes values;
+    at ``level`` >= 3 they go to the LZ4-HC call of ``fn_name``'s section."""
     n = len(srcs)
     dev = srcs[0].device if n else torch.device("cuda", torch.cuda.current_device())
     if stream is None:
@@ -229,14 +231,15 @@ def _batch(fn_name, srcs, caps, null_caps, max_chunk, stream, level=0, workspace
         st = ctypes.c_void_p(ts.cuda_stream)
         cap_arg = ctypes.c_void_p(None if null_caps else d_cap)
         if level >= 3:
-            if dict_args is not None:   # (dictionary, size, HC state): section 5c
+            if dict_args is not None:   # (dictionary, size, HC state): section 5c; the set's arrays: section 5e
                 if workspace is None:
                     workspace = batch_compress_dict_workspace(max_chunk, n, level, device=dev)
-                fn_name = "lz4mtHipCompressBatchDictHC"
-                r = lib.lz4mtHipCompressBatchDictHC(ctypes.c_void_p(d_src), ctypes.c_void_p(d_sz), max_chunk, n,
-                                                    ctypes.c_void_p(d_dst), cap_arg, ctypes.c_void_p(sizes.data_ptr()),
-                                                    *dict_args, level, ctypes.c_void_p(workspace.data_ptr()),
-                                                    workspace.numel(), st)
+                fn_name = "lz4mtHipCompressBatchDictSetHC" if fn_name == "lz4mtHipCompressBatchDictSet" else \
+                    "lz4mtHipCompressBatchDictHC"
+                r = getattr(lib, fn_name)(ctypes.c_void_p(d_src), ctypes.c_void_p(d_sz), max_chunk, n,
+                                          ctypes.c_void_p(d_dst), cap_arg, ctypes.c_void_p(sizes.data_ptr()),
+                                          *dict_args, level, ctypes.c_void_p(workspace.data_ptr()),
+                                          workspace.numel(), st)
                 if r != Result.OK:
                     raise Lz4MtError(r, fn_name)
                 return [back[o:o + c] for o, c in zip(offs, caps)], sizes
@@ -453,14 +456,22 @@ class PreparedDictSet:
     ``ptrs`` (int64) and ``sizes`` (int32, u32 bit patterns): the device
     arrays lz4mtHipDictSetPrepare read, and ``states``: a uint8 device tensor
     of ``len(dictionaries)`` states of lz4mtHipDictStateSize bytes each, or
-    None when the set was built for decoding only."""
-    __slots__ = ("dictionaries", "ptrs", "sizes", "states")
+    None when the set was built for decoding only.  ``kind``: "fast"
+    (prepare_dict_set, for compress_batch_dict_set) or "hc"
+    (prepare_dict_set_hc: states of lz4mtHipDictStateSizeHC bytes, for
+    compress_batch_dict_set_hc); ``is_hc`` tells them apart."""
+    __slots__ = ("dictionaries", "ptrs", "sizes", "states", "kind")
 
-    def __init__(self, dictionaries, ptrs, sizes, states):
+    def __init__(self, dictionaries, ptrs, sizes, states, kind="fast"):
         self.dictionaries = dictionaries
         self.ptrs = ptrs
         self.sizes = sizes
         self.states = states
+        self.kind = kind
+
+    @property
+    def is_hc(self):
+        return self.kind == "hc"
 
     def __len__(self):
         return len(self.dictionaries)
@@ -474,9 +485,10 @@ def _torch_stream(stream, dev):
     return torch.cuda.ExternalStream(int(stream), device=dev)
 
 
-def _dict_set(dictionaries, stream, states):
+def _dict_set(dictionaries, stream, states, hc=False):
     """The device arrays of a set (uploaded on ``stream`` from pinned memory,
-    no synchronisation) and, with ``states``, lz4mtHipDictSetPrepare."""
+    no synchronisation) and, with ``states``, lz4mtHipDictSetPrepare (``hc``:
+    lz4mtHipDictSetPrepareHC)."""
     dictionaries = list(dictionaries)
     for i, d in enumerate(dictionaries):
         _check_dev(d, f"dictionaries[{i}]")
@@ -495,14 +507,15 @@ def _dict_set(dictionaries, stream, states):
         ptrs, sizes = desc[:8 * k].view(torch.int64), desc[8 * k:12 * k].view(torch.int32)
         st = None
         if states:
-            st = torch.empty(k * int(lib.lz4mtHipDictStateSize()), dtype=torch.uint8, device=dev)
+            size_fn, prep = (lib.lz4mtHipDictStateSizeHC, "lz4mtHipDictSetPrepareHC") if hc else \
+                (lib.lz4mtHipDictStateSize, "lz4mtHipDictSetPrepare")
+            st = torch.empty(k * int(size_fn()), dtype=torch.uint8, device=dev)
             assert st.data_ptr() % 256 == 0
-            r = lib.lz4mtHipDictSetPrepare(ctypes.c_void_p(ptrs.data_ptr()), ctypes.c_void_p(sizes.data_ptr()), k,
-                                           ctypes.c_void_p(st.data_ptr()), st.numel(),
-                                           ctypes.c_void_p(ts.cuda_stream))
+            r = getattr(lib, prep)(ctypes.c_void_p(ptrs.data_ptr()), ctypes.c_void_p(sizes.data_ptr()), k,
+                                   ctypes.c_void_p(st.data_ptr()), st.numel(), ctypes.c_void_p(ts.cuda_stream))
             if r != Result.OK:
-                raise Lz4MtError(r, "lz4mtHipDictSetPrepare")
-    return PreparedDictSet(dictionaries, ptrs, sizes, st)
+                raise Lz4MtError(r, prep)
+    return PreparedDictSet(dictionaries, ptrs, sizes, st, "hc" if hc else "fast")
 
 
 def prepare_dict_set(dictionaries, stream=None):
@@ -511,6 +524,15 @@ def prepare_dict_set(dictionaries, stream=None):
     alignment) with one kernel on ``stream``.  Returns a PreparedDictSet.
     Does not synchronise."""
     return _dict_set(dictionaries, stream, True)
+
+
+def prepare_dict_set_hc(dictionaries, stream=None):
+    """lz4mtHipDictSetPrepareHC: what prepare_dict_hc does, for every tensor of
+    ``dictionaries``, one workgroup per dictionary on ``stream``.  The states
+    serve every level from 3 up.  Returns a PreparedDictSet of kind "hc" (for
+    compress_batch_dict_set_hc and decompress_batch_dict_set).  Does not
+    synchronise."""
+    return _dict_set(dictionaries, stream, True, hc=True)
 
 
 def _which(which, n, k, dev, ts):
@@ -541,9 +563,32 @@ def compress_batch_dict_set(chunks, prepared, which, caps=None, stream=None):
     decompress_batch_dict_set, the same set and the same ``which``.  Does not
     synchronise: ``chunks`` and ``prepared`` must stay alive until ``stream``
     has run the call, and ``stream`` must be ordered after the one
-    prepare_dict_set ran on."""
+    prepare_dict_set ran on.  A PreparedDictSet of kind "hc"
+    (prepare_dict_set_hc) is a TypeError: LZ4-HC is compress_batch_dict_set_hc."""
+    return _compress_batch_dict_set(chunks, prepared, which, caps, stream, 0, None)
+
+
+def compress_batch_dict_set_hc(chunks, prepared, which, level, caps=None, stream=None, workspace=None):
+    """lz4mtHipCompressBatchDictSetHC: compress_batch_dict_hc at ``level``
+    3..12 with a dictionary per chunk, in one call: chunk ``i`` gets
+    dictionary ``which[i]`` of ``prepared`` (prepare_dict_set_hc; a set of kind
+    "fast" is a TypeError), or compress_batch's bytes at ``level`` when
+    ``which[i]`` is None.  Everything else as compress_batch_dict_set;
+    ``workspace`` as for compress_batch_dict_hc."""
+    level = int(level)
+    if level < 3:
+        raise ValueError("compress_batch_dict_set_hc: level 3..12 (the fast codec is compress_batch_dict_set)")
+    return _compress_batch_dict_set(chunks, prepared, which, caps, stream, level, workspace)
+
+
+def _compress_batch_dict_set(chunks, prepared, which, caps, stream, level, workspace):
     if not isinstance(prepared, PreparedDictSet) or prepared.states is None:
-        raise TypeError("prepared must come from prepare_dict_set")
+        raise TypeError("prepared must come from prepare_dict_set / prepare_dict_set_hc")
+    if prepared.is_hc != (level >= 3):
+        raise TypeError("compress_batch_dict_set takes a prepare_dict_set set, "
+                        "compress_batch_dict_set_hc a prepare_dict_set_hc set")
+    if workspace is not None:
+        _check_dev(workspace, "workspace")
     chunks = list(chunks)
     for i, c in enumerate(chunks):
         _check_dev(c, f"chunks[{i}]")
@@ -562,13 +607,15 @@ def compress_batch_dict_set(chunks, prepared, which, caps=None, stream=None):
     idx = _which(which, len(chunks), len(prepared), dev, ts)
     dict_args = (ctypes.c_void_p(prepared.ptrs.data_ptr()), ctypes.c_void_p(prepared.sizes.data_ptr()),
                  len(prepared), ctypes.c_void_p(prepared.states.data_ptr()), ctypes.c_void_p(idx.data_ptr()))
-    return _batch("lz4mtHipCompressBatchDictSet", chunks, caps, null_caps, big, ts, dict_args=dict_args)
+    return _batch("lz4mtHipCompressBatchDictSet", chunks, caps, null_caps, big, ts, level, workspace,
+                  dict_args=dict_args)
 
 
 def decompress_batch_dict_set(blocks, caps, dictionaries, which, stream=None):
     """lz4mtHipDecompressBatchDictSet: decompress_batch_dict with a dictionary
     per block, in one launch.  ``dictionaries``: the PreparedDictSet the
-    blocks were compressed with, or a list of uint8 device tensors;
+    blocks were compressed with (of either kind: only its dictionaries are
+    used), or a list of uint8 device tensors;
     ``which[i]``: the index of block ``i``'s dictionary, or None for a block
     made without one.  Does not synchronise."""
     blocks = list(blocks)

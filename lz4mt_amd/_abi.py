@@ -117,6 +117,10 @@ PROTOTYPES = {
                                              c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p]),
     "lz4mtHipDecompressBatchDictSet": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
                                                c_void_p, c_uint32, c_void_p, c_void_p]),
+    "lz4mtHipDictSetPrepareHC": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint64, c_void_p]),
+    "lz4mtHipCompressBatchDictSetHC": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_int, c_void_p,
+                                               c_uint64, c_void_p]),
     "lz4mtHipFrameBound": (c_uint64, [c_uint64, SD_P]),
     "lz4mtHipCompressWorkspaceSize": (c_uint64, [c_uint64, SD_P]),
     "lz4mtHipCompressFrame": (c_int, [c_void_p, c_uint64, c_void_p, c_uint64, ctypes.POINTER(c_uint64), SD_P,

@@ -289,6 +289,21 @@ hipError_t launch_encode_hc_batch_dict(const uint8_t* const* srcPtrs, const uint
                                        uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps,
                                        int32_t* outSizes, const uint8_t* dictEnd, uint32_t E, const uint8_t* state,
                                        int level, uint8_t* ws, uint32_t slots, hipStream_t st);
+// The same with a set of dictionaries and an index per chunk (section 5e;
+// k_hc_dict_set_prepare, k_hc_prev_batch_dict_set, k_encode_hc_batch_dict_set /
+// k_encode_hc_opt_batch_dict_set).  dictPtrs / dictSizes / chunkDict are
+// device arrays: the kernels compute the dictionary's end and its effective
+// size themselves.  State k stands at states + k * kHcDictStateBytes (256-byte
+// aligned) and is what launch_hc_dict_prepare writes for dictionary k.
+// chunkDict[i] = kBatchNoDict: no dictionary (states may then be null).
+hipError_t launch_hc_dict_set_prepare(const uint8_t* const* dictPtrs, const uint32_t* dictSizes, uint32_t nDicts,
+                                      uint8_t* states, hipStream_t st);
+hipError_t launch_encode_hc_batch_dict_set(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
+                                           uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps,
+                                           int32_t* outSizes, const uint8_t* const* dictPtrs,
+                                           const uint32_t* dictSizes, uint32_t nDicts, const uint8_t* states,
+                                           const uint32_t* chunkDict, int level, uint8_t* ws, uint32_t slots,
+                                           hipStream_t st);
 // -BD at level >= 3: segments [begin[k], end[k]) of src (begin >= -64 KiB),
 // blockSeg[b] = block b's segment; delta0 = chain scratch for src[0], with
 // 64 Ki entries before it.

@@ -750,6 +750,51 @@ extern "C" Lz4MtResult lz4mtHipCompressBatchDictHC(const void* const* d_srcPtrs,
     return LZ4MT_RESULT_OK;
 }
 
+// LZ4-HC with a set of dictionaries and an index per chunk (section 5e).  The
+// host reads none of the arrays: trimming, the index check and the state guard
+// are the kernels'.
+extern "C" Lz4MtResult lz4mtHipDictSetPrepareHC(const void* const* d_dictPtrs, const uint32_t* d_dictSizes,
+                                                uint32_t nDicts, void* d_statesHC, uint64_t statesSize,
+                                                void* stream) {
+    if (nDicts && (!d_dictPtrs || !d_dictSizes)) return LZ4MT_RESULT_BAD_ARG;
+    if (nDicts && (!d_statesHC || (reinterpret_cast<uintptr_t>(d_statesHC) & 255) != 0 ||
+                   statesSize < (uint64_t)nDicts * kHcDictStateBytes))
+        return LZ4MT_RESULT_BAD_ARG;
+    if (!have_device()) return LZ4MT_RESULT_ERROR;
+    if (nDicts == 0) return LZ4MT_RESULT_OK;
+    HIPCHK(launch_hc_dict_set_prepare(reinterpret_cast<const uint8_t* const*>(d_dictPtrs), d_dictSizes, nDicts,
+                                      static_cast<uint8_t*>(d_statesHC), static_cast<hipStream_t>(stream)));
+    return LZ4MT_RESULT_OK;
+}
+
+extern "C" Lz4MtResult lz4mtHipCompressBatchDictSetHC(const void* const* d_srcPtrs, const uint32_t* d_srcSizes,
+                                                      uint32_t maxChunkBytes, uint32_t nChunks,
+                                                      void* const* d_dstPtrs, const uint32_t* d_dstCaps,
+                                                      int32_t* d_outSizes, const void* const* d_dictPtrs,
+                                                      const uint32_t* d_dictSizes, uint32_t nDicts,
+                                                      const void* d_statesHC, const uint32_t* d_chunkDict, int level,
+                                                      void* d_workspace, uint64_t workspaceSize, void* stream) {
+    if (nChunks && (!d_srcPtrs || !d_srcSizes || !d_dstPtrs || !d_outSizes || !d_chunkDict))
+        return LZ4MT_RESULT_BAD_ARG;
+    if (maxChunkBytes > LZ4MT_HIP_BATCH_MAX_CHUNK) return LZ4MT_RESULT_BAD_ARG;
+    if (level < 3) return LZ4MT_RESULT_BAD_ARG;
+    if (nDicts && (!d_dictPtrs || !d_dictSizes)) return LZ4MT_RESULT_BAD_ARG;
+    if (nDicts && (!d_statesHC || (reinterpret_cast<uintptr_t>(d_statesHC) & 255) != 0)) return LZ4MT_RESULT_BAD_ARG;
+    const uint64_t slot = hc_batch_slot_bytes(maxChunkBytes, level);
+    if (nChunks && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0 || workspaceSize < slot))
+        return LZ4MT_RESULT_BAD_ARG;
+    if (!have_device()) return LZ4MT_RESULT_ERROR;
+    if (nChunks == 0) return LZ4MT_RESULT_OK;
+    const uint32_t slots = (uint32_t)std::min<uint64_t>(workspaceSize / slot, kHcBatchSlots);
+    HIPCHK(launch_encode_hc_batch_dict_set(
+        reinterpret_cast<const uint8_t* const*>(d_srcPtrs), d_srcSizes, maxChunkBytes, nChunks,
+        reinterpret_cast<uint8_t* const*>(d_dstPtrs), d_dstCaps, d_outSizes,
+        reinterpret_cast<const uint8_t* const*>(d_dictPtrs), d_dictSizes, nDicts,
+        static_cast<const uint8_t*>(d_statesHC), d_chunkDict, level, static_cast<uint8_t*>(d_workspace), slots,
+        static_cast<hipStream_t>(stream)));
+    return LZ4MT_RESULT_OK;
+}
+
 // ===========================================================================
 // 2. device-resident frame engine
 // ===========================================================================

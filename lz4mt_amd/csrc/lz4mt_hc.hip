@@ -1305,7 +1305,145 @@ __global__ void __launch_bounds__(64) k_encode_hc_opt_batch_dict(const uint8_t* 
 }
 
 // ---------------------------------------------------------------------------
-// Split parse of large blocks.  A 4 MiB block is one serial hashChain parse
+// The same with a set of dictionaries and an index per chunk (lz4mt_hip.h
+// section 5e, lz4mtHipDictSetPrepareHC / lz4mtHipCompressBatchDictSetHC).
+// The dictionaries' pointers and sizes are device arrays, so what the host
+// does for section 5c happens here: E = min(size, 64 KiB) and the
+// dictionary's end, pointer + size in 64-bit arithmetic.  State k stands
+// kHcDictStateBytes behind state k - 1 and is byte for byte what
+// k_hc_dict_prepare writes for dictionary k.
+// kHcDictStateBad: the recorded size of a dictionary that has a size and no
+// pointer.  No effective size equals it, so hc_dict_state_ok refuses it for
+// every dictionary.
+// kBatchNoDict is served as an HcDictBlock with E = 0 behind a chain built
+// from an empty table (kPrevPlain: the deltas k_hc_prev_batch writes): no
+// position lies below E, so neither `dict` nor `ddl` is ever read, and the
+// parse writes lz4mtHipCompressBatchEx's bytes (section 5c's E < 4 rule,
+// pinned by the fixture's 0-byte dictionary).  It needs no state.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kHcDictStateBad = 0xFFFFFFFFu;
+static_assert(kHcDictStateBad > kDictWindow, "no effective size");
+
+// k_hc_dict_prepare's work, workgroup k for dictionary k (pointer and size are
+// uniform scalar loads).  A dictionary with a size and no pointer is treated
+// as empty and recorded as kHcDictStateBad.
+__global__ void __launch_bounds__(kPrevThreads) k_hc_dict_set_prepare(const uint8_t* const* __restrict__ dictPtrs,
+                                                                      const uint32_t* __restrict__ dictSizes,
+                                                                      uint8_t* __restrict__ states) {
+    __shared__ uint32_t last[1u << kHashLog];
+    __shared__ uint8_t dd[4 * 1024];
+    __shared__ __attribute__((aligned(16))) uint32_t ring[2048];
+    const uint32_t t = threadIdx.x, k = blockIdx.x;
+    const uint32_t size = dictSizes[k];
+    const uint8_t* dp = dictPtrs[k];
+    const bool bad = !dp && size != 0;
+    const uint32_t E = bad ? 0u : (size < kDictWindow ? size : kDictWindow);
+    const uint8_t* dictEnd = dp + size;
+    uint8_t* state = states + (uint64_t)k * kHcDictStateBytes;
+    g_u16* links = (g_u16*)(state + kHcDictLinksAt);
+    hc_prev_range<kPrevDict>((g_cu8*)dictEnd - E, E, links, (l_u32*)last, (l_u8*)dd, (l_u32*)ring);
+    __syncthreads();
+    uint32_t* heads = (uint32_t*)(state + kHcDictHeadsAt);
+    for (uint32_t i = t; i < (1u << kHashLog); i += kPrevThreads) heads[i] = last[i];
+    for (uint32_t p = (E >= 4 ? E - 3 : 0u) + t; p < kDictWindow + 128; p += kPrevThreads) links[p] = 0;
+    uint32_t* w = (uint32_t*)state;
+    for (uint32_t i = t; i < kHcDictHeadsAt / 4; i += kPrevThreads)
+        w[i] = i == 0 ? kHcDictMagic : i == 1 ? (bad ? kHcDictStateBad : E) : i == 4096 ? 0xFFFFFFFFu : 0u;
+}
+
+// The dictionary of chunk blockIdx.x (all uniform: scalar loads).  ok: the
+// chunk has no dictionary (state == nullptr, E = 0), or names dictionary k <
+// nDicts that has a pointer or no size and whose state k is an HC state for
+// its effective size.  The one place the chain kernel and the parse kernels
+// take a dictionary's refusal from, so a parse wave never reads a slot whose
+// chain was not written for it in this round.
+struct HcSetDict {
+    const uint8_t* dictEnd;
+    const uint8_t* state;   // nullptr: no dictionary
+    uint32_t E;
+    bool ok;
+};
+__device__ __forceinline__ HcSetDict hc_set_dict(const uint32_t* __restrict__ chunkDict,
+                                                 const uint8_t* const* __restrict__ dictPtrs,
+                                                 const uint32_t* __restrict__ dictSizes, uint32_t nDicts,
+                                                 const uint8_t* __restrict__ states) {
+    const uint32_t k = chunkDict[blockIdx.x];
+    HcSetDict r{nullptr, nullptr, 0u, k == kBatchNoDict};
+    if (k < nDicts) {   // (kBatchNoDict is no index: nDicts <= 0xFFFFFFFF)
+        const uint32_t size = dictSizes[k];
+        const uint8_t* dp = dictPtrs[k];
+        r.E = size < kDictWindow ? size : kDictWindow;
+        r.dictEnd = dp + size;
+        r.state = states + (uint64_t)k * kHcDictStateBytes;
+        r.ok = (dp || size == 0) && hc_dict_state_ok(r.state, r.E);
+    }
+    return r;
+}
+
+// k_hc_prev_batch_dict with the heads read from the chunk's own state; without
+// a dictionary the chain of k_hc_prev_batch.  Refusal and choice are
+// workgroup-uniform (blockIdx.x only) and come before the first barrier.
+__global__ void __launch_bounds__(kPrevThreads) k_hc_prev_batch_dict_set(
+    const uint8_t* const* __restrict__ srcPtrs, const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
+    uint8_t* const* __restrict__ dstPtrs, uint8_t* __restrict__ ws, uint64_t slotBytes,
+    const uint8_t* const* __restrict__ dictPtrs, const uint32_t* __restrict__ dictSizes, uint32_t nDicts,
+    const uint8_t* __restrict__ states, const uint32_t* __restrict__ chunkDict) {
+    __shared__ uint32_t last[1u << kHashLog];
+    __shared__ uint8_t dd[4 * 1024];
+    __shared__ __attribute__((aligned(16))) uint32_t ring[2048];
+    const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, nullptr);
+    const HcSetDict D = hc_set_dict(chunkDict, dictPtrs, dictSizes, nDicts, states);
+    if (c.bad || !D.ok) return;
+    g_u16* dl = (g_u16*)(ws + (uint64_t)blockIdx.x * slotBytes);
+    if (D.state)
+        hc_prev_range<kPrevChunk>(c.s, c.n, dl, (l_u32*)last, (l_u8*)dd, (l_u32*)ring,
+                                  (const uint32_t*)(D.state + kHcDictHeadsAt), D.E);
+    else
+        hc_prev_range<kPrevPlain>(c.s, c.n, dl, (l_u32*)last, (l_u8*)dd, (l_u32*)ring);
+}
+
+__device__ __forceinline__ HcDictBlock hc_set_block(const BatchChunk& c, const uint8_t* slot, const HcSetDict& D,
+                                                    uint32_t attempts, bool pattern) {
+    return HcDictBlock{c.s, c.n, (g_cu16*)slot, (g_cu8*)D.dictEnd - D.E, (g_cu16*)(D.state + kHcDictLinksAt), D.E,
+                       attempts, pattern};
+}
+
+// Levels 3..9 / 10..12: k_encode_hc_batch_dict / k_encode_hc_opt_batch_dict with the dictionary of hc_set_dict
+__global__ void __launch_bounds__(64) k_encode_hc_batch_dict_set(
+    const uint8_t* const* __restrict__ srcPtrs, const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
+    uint8_t* const* __restrict__ dstPtrs, const uint32_t* __restrict__ dstCaps, int32_t* __restrict__ outSizes,
+    const uint8_t* __restrict__ ws, uint64_t slotBytes, uint32_t maxAttempts,
+    const uint8_t* const* __restrict__ dictPtrs, const uint32_t* __restrict__ dictSizes, uint32_t nDicts,
+    const uint8_t* __restrict__ states, const uint32_t* __restrict__ chunkDict) {
+    const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, dstCaps);
+    const HcSetDict D = hc_set_dict(chunkDict, dictPtrs, dictSizes, nDicts, states);
+    int32_t r = kBatchBadChunk;
+    if (!c.bad && D.ok) {
+        const HcDictBlock B = hc_set_block(c, ws + (uint64_t)blockIdx.x * slotBytes, D, maxAttempts, maxAttempts > 128);
+        r = encode_block_hc(B, c.d, c.cap);
+    }
+    if (laneid() == 0) outSizes[blockIdx.x] = r;
+}
+
+__global__ void __launch_bounds__(64) k_encode_hc_opt_batch_dict_set(
+    const uint8_t* const* __restrict__ srcPtrs, const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
+    uint8_t* const* __restrict__ dstPtrs, const uint32_t* __restrict__ dstCaps, int32_t* __restrict__ outSizes,
+    uint8_t* ws, uint64_t slotBytes, uint64_t tableAt, uint32_t nbSearches, int32_t sufficientLen, int32_t fullUpdate,
+    const uint8_t* const* __restrict__ dictPtrs, const uint32_t* __restrict__ dictSizes, uint32_t nDicts,
+    const uint8_t* __restrict__ states, const uint32_t* __restrict__ chunkDict) {
+    const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, dstCaps);
+    const HcSetDict D = hc_set_dict(chunkDict, dictPtrs, dictSizes, nDicts, states);
+    int32_t r = kBatchBadChunk;
+    if (!c.bad && D.ok) {
+        uint8_t* slot = ws + (uint64_t)blockIdx.x * slotBytes;
+        const HcDictBlock B = hc_set_block(c, slot, D, nbSearches, true);
+        r = encode_block_hc_opt(B, c.d, c.cap, hc_opt_at(slot + tableAt, 0), sufficientLen, fullUpdate != 0);
+    }
+    if (laneid() == 0) outSizes[blockIdx.x] = r;
+}
+
+// ---------------------------------------------------------------------------
+// Split parse of large blocks. A 4 MiB block is one serial hashChain parse
 // (k_encode_hc: 2048 waves for 8 GiB, latency-bound); here stream j of a
 // block starts its own parse at M_j = j * sub (j = 0: the block start) and
 // the streams are spliced where they meet:
@@ -1725,6 +1863,55 @@ hipError_t launch_encode_hc_batch_dict(const uint8_t* const* srcPtrs, const uint
         else
             hipLaunchKernelGGL(k_encode_hc_batch_dict, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, maxChunk,
                                dstPtrs + o, caps, outSizes + o, (const uint8_t*)ws, slotBytes, att, dictEnd, E, state);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        o += g;
+    }
+    return hipSuccess;
+}
+
+// The same with a set of dictionaries (section 5e): every array is device
+// memory; state k at states + k * kHcDictStateBytes, 256-byte aligned.  One
+// workgroup per dictionary, a launch per kHcSetGrid dictionaries.
+constexpr uint32_t kHcSetGrid = 1u << 30;
+hipError_t launch_hc_dict_set_prepare(const uint8_t* const* dictPtrs, const uint32_t* dictSizes, uint32_t nDicts,
+                                      uint8_t* states, hipStream_t st) {
+    for (uint32_t o = 0; o < nDicts;) {
+        const uint32_t g = std::min(nDicts - o, kHcSetGrid);
+        hipLaunchKernelGGL(k_hc_dict_set_prepare, dim3(g), dim3(kPrevThreads), 0, st, dictPtrs + o, dictSizes + o,
+                           states + (uint64_t)o * kHcDictStateBytes);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        o += g;
+    }
+    return hipSuccess;
+}
+
+// launch_encode_hc_batch_dict's rounds and slots; a round slices chunkDict with
+// the other chunk arrays, the dictionary arrays and the states are the call's
+hipError_t launch_encode_hc_batch_dict_set(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
+                                           uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps,
+                                           int32_t* outSizes, const uint8_t* const* dictPtrs,
+                                           const uint32_t* dictSizes, uint32_t nDicts, const uint8_t* states,
+                                           const uint32_t* chunkDict, int level, uint8_t* ws, uint32_t slots,
+                                           hipStream_t st) {
+    if (level < 3 || slots == 0 || !ws || !chunkDict) return hipErrorInvalidValue;
+    slots = std::min(slots, kHcBatchSlots);
+    const uint32_t att = hc_attempts(level);
+    const int lv = level > 12 ? 12 : level;
+    const int32_t tl = lv == 10 ? 64 : lv == 11 ? 128 : kOptNum, fu = lv == 12 ? 1 : 0;   // as launch_encode_hc
+    const uint64_t slotBytes = hc_batch_slot_bytes(maxChunk, level), tableAt = hc_batch_delta_bytes(maxChunk);
+    for (uint32_t o = 0; o < nChunks;) {
+        const uint32_t g = std::min(nChunks - o, slots);
+        const uint32_t* caps = dstCaps ? dstCaps + o : nullptr;
+        hipLaunchKernelGGL(k_hc_prev_batch_dict_set, dim3(g), dim3(kPrevThreads), 0, st, srcPtrs + o, srcSizes + o,
+                           maxChunk, dstPtrs + o, ws, slotBytes, dictPtrs, dictSizes, nDicts, states, chunkDict + o);
+        if (lv >= 10)
+            hipLaunchKernelGGL(k_encode_hc_opt_batch_dict_set, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o,
+                               maxChunk, dstPtrs + o, caps, outSizes + o, ws, slotBytes, tableAt, att, tl, fu, dictPtrs,
+                               dictSizes, nDicts, states, chunkDict + o);
+        else
+            hipLaunchKernelGGL(k_encode_hc_batch_dict_set, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o,
+                               maxChunk, dstPtrs + o, caps, outSizes + o, (const uint8_t*)ws, slotBytes, att, dictPtrs,
+                               dictSizes, nDicts, states, chunkDict + o);
         if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
         o += g;
     }

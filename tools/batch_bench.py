@@ -28,7 +28,7 @@ lz4mtHipCompressBatchEx call at the same level on the same chunks for the
 time ("plain_*"), and the fast dictionary call lz4mtHipCompressBatchDict with
 the same dictionary for the ratio ("fast_dict_*").
 
---dicts N with --dict-kib K (the fast codec only) also times the calls with a
+--dicts N with --dict-kib K (the fast codec) also times the calls with a
 set of dictionaries (lz4mtHipCompressBatchDictSet /
 lz4mtHipDecompressBatchDictSet; lz4mtHipDictSetPrepare on its own): N
 dictionaries of K KiB, chunk i using dictionary i % N.  The N dictionaries
@@ -37,6 +37,16 @@ the set calls then do the shared-dictionary call's work on the same chunks
 (the sizes are compared) and differ from it in the per-chunk loads and in the
 memory the tables and dictionaries are read from.  The yardstick is the
 shared-dictionary call in the same row ("set_*_over_shared").
+
+--dicts N with --dict-kib K and --level L >= 3 times the LZ4-HC set call
+(lz4mtHipCompressBatchDictSetHC; lz4mtHipDictSetPrepareHC on its own) on the
+same layout: N allocations of the same K KiB, N states, chunk i using
+dictionary i % N.  Two yardsticks on the same chunks in the same run: the
+shared-dictionary call lz4mtHipCompressBatchDictHC ("set_compress_over_shared")
+and N calls of it, one per dictionary over that dictionary's chunks, what a
+caller without the set call has to issue ("separate_*",
+"set_compress_over_separate").  The sizes of both are compared with the shared
+call's.
 
 --rows picks the chunkings to run (4KiB, 64KiB, 1MiB, ragged; default all).
 
@@ -165,7 +175,7 @@ def batch_row(name, src, sizes, reps, level=0, slots=0, dct=None):
         dbytes = int(csz.sum().item())
         sset = {}
         if dset is not None:   # the same chunks through the set calls, chunk i with dictionary i % N
-            d_ptrs, d_sizes, states, nd = dset
+            d_ptrs, d_sizes, states, nd, copies = dset
             which = torch.from_numpy((np.arange(n, dtype=np.int64) % nd).astype(np.int32)).cuda()
             shared_sizes = csz.clone()
 
@@ -182,18 +192,27 @@ def batch_row(name, src, sizes, reps, level=0, slots=0, dct=None):
                                                          P(d_sizes.data_ptr()), nd, P(which.data_ptr()), st)
                 assert r == 0, r
 
-            csz.zero_()
-            back.zero_()
-            es = timed(enc_s, reps)
-            dz = timed(dec_s, reps)
-            assert torch.equal(csz, shared_sizes), name   # the same dictionary bytes: the same blocks
-            round_trip()
-            sset = {"dicts": nd, "set_kernel": "k_encode_batch_dict_set / k_decode_batch_dict_set",
-                    "set_compress_ms": round(es[0], 3), "set_compress_ms_min_max": [round(es[1], 3), round(es[2], 3)],
-                    "set_decompress_ms": round(dz[0], 3),
-                    "set_decompress_ms_min_max": [round(dz[1], 3), round(dz[2], 3)],
-                    "set_compress_over_shared": round(es[0] / ed[0], 4),
-                    "set_decompress_over_shared": round(dz[0] / dd[0], 4)}
+            if level >= 3:
+                sset = hc_set_part(name, reps, level, n, max_chunk, nd, copies, d_ptrs, d_sizes, states, which, ws, st,
+                                   sp, sz, cp, csz, soff + src.data_ptr(), doff + comp.data_ptr(), sizes,
+                                   shared_sizes, ed)
+                back.zero_()
+                timed(dec_s, 1, warm=0)   # the set call's blocks through the set decoder, once
+                round_trip()
+            else:
+                csz.zero_()
+                back.zero_()
+                es = timed(enc_s, reps)
+                dz = timed(dec_s, reps)
+                assert torch.equal(csz, shared_sizes), name   # the same dictionary bytes: the same blocks
+                round_trip()
+                sset = {"dicts": nd, "set_kernel": "k_encode_batch_dict_set / k_decode_batch_dict_set",
+                        "set_compress_ms": round(es[0], 3),
+                        "set_compress_ms_min_max": [round(es[1], 3), round(es[2], 3)],
+                        "set_decompress_ms": round(dz[0], 3),
+                        "set_decompress_ms_min_max": [round(dz[1], 3), round(dz[2], 3)],
+                        "set_compress_over_shared": round(es[0] / ed[0], 4),
+                        "set_decompress_over_shared": round(dz[0] / dd[0], 4)}
         kernel, plain = "k_encode_batch_dict", "k_encode_batch16" if max_chunk < 65547 else "k_encode_batch"
         if level >= 3:
             kernel = "k_hc_prev_batch_dict + " + ("k_encode_hc_opt_batch_dict" if level >= 10 else "k_encode_hc_batch_dict")
@@ -220,6 +239,56 @@ def batch_row(name, src, sizes, reps, level=0, slots=0, dct=None):
             "compress_gib_s": round(gib / (e[0] / 1e3), 2),
             "decompress_ms": round(d[0], 3), "decompress_ms_min_max": [round(d[1], 3), round(d[2], 3)],
             "decompress_gib_s": round(gib / (d[0] / 1e3), 2)}
+
+
+def hc_set_part(name, reps, level, n, max_chunk, nd, copies, d_ptrs, d_sizes, states, which, ws, st, sp, sz, cp, csz,
+                src_ptrs, dst_ptrs, sizes, shared_sizes, ed):
+    """lz4mtHipCompressBatchDictSetHC, and nd calls of lz4mtHipCompressBatchDictHC over each dictionary's
+    chunks (the arrays permuted so that a dictionary's chunks stand together), against the shared call ``ed``."""
+    S = L.lib.lz4mtHipDictStateSizeHC()
+
+    def enc_s():
+        r = L.lib.lz4mtHipCompressBatchDictSetHC(P(sp.data_ptr()), P(sz.data_ptr()), max_chunk, n, P(cp.data_ptr()),
+                                                 None, P(csz.data_ptr()), P(d_ptrs.data_ptr()), P(d_sizes.data_ptr()),
+                                                 nd, P(states.data_ptr()), P(which.data_ptr()), level,
+                                                 P(ws.data_ptr()), ws.numel(), st)
+        assert r == 0, r
+
+    own = np.arange(n, dtype=np.int64) % nd
+    perm = np.argsort(own, kind="stable")
+    counts = np.bincount(own, minlength=nd)
+    starts = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    sp_p = torch.from_numpy(src_ptrs[perm]).cuda()
+    cp_p = torch.from_numpy(dst_ptrs[perm]).cuda()
+    sz_p = torch.from_numpy(sizes[perm].astype(np.uint32).view(np.int32)).cuda()
+    csz_p = torch.zeros(n, dtype=torch.int32, device="cuda")
+
+    def enc_k():
+        for j in range(nd):
+            o, g = int(starts[j]), int(counts[j])
+            if g == 0:
+                continue
+            r = L.lib.lz4mtHipCompressBatchDictHC(P(sp_p.data_ptr() + 8 * o), P(sz_p.data_ptr() + 4 * o), max_chunk, g,
+                                                  P(cp_p.data_ptr() + 8 * o), None, P(csz_p.data_ptr() + 4 * o),
+                                                  P(copies[j].data_ptr()), copies[j].numel(),
+                                                  P(states.data_ptr() + j * S), level, P(ws.data_ptr()), ws.numel(),
+                                                  st)
+            assert r == 0, r
+
+    ek = timed(enc_k, reps)
+    assert torch.equal(csz_p, shared_sizes[torch.from_numpy(perm).cuda()]), name
+    csz.zero_()
+    es = timed(enc_s, reps)
+    assert torch.equal(csz, shared_sizes), name   # the same dictionary bytes: the same blocks
+    return {"dicts": nd,
+            "set_kernel": "k_hc_prev_batch_dict_set + " + ("k_encode_hc_opt_batch_dict_set" if level >= 10 else
+                                                           "k_encode_hc_batch_dict_set"),
+            "set_compress_ms": round(es[0], 3), "set_compress_ms_min_max": [round(es[1], 3), round(es[2], 3)],
+            "separate_calls": int((counts > 0).sum()),
+            "separate_compress_ms": round(ek[0], 3),
+            "separate_compress_ms_min_max": [round(ek[1], 3), round(ek[2], 3)],
+            "set_compress_over_shared": round(es[0] / ed[0], 4),
+            "set_compress_over_separate": round(es[0] / ek[0], 4)}
 
 
 def frame_row(src, bid, reps, level=0):
@@ -266,8 +335,8 @@ def main():
     want = set(a.rows.split(","))
     if not want <= {"4KiB", "64KiB", "1MiB", "ragged"}:
         sys.exit("--rows: a comma-separated subset of 4KiB,64KiB,1MiB,ragged")
-    if a.dicts and (not a.dict_kib or a.level >= 3 or a.dicts < 0):
-        sys.exit("--dicts: a count of dictionaries, with --dict-kib and the fast codec")
+    if a.dicts and (not a.dict_kib or a.dicts < 0):
+        sys.exit("--dicts: a count of dictionaries, with --dict-kib")
     if not torch.cuda.is_available():
         sys.exit("batch_bench.py needs a HIP device")
     n = int(a.gib * 2**30) & ~((1 << 20) - 1)
@@ -301,21 +370,23 @@ def main():
                          "prepare_ms_min_max": [round(ph[1], 4), round(ph[2], 4)]})
         dset = None
         if a.dicts:   # N allocations of the same bytes (alive until main returns), N states
-            copies =[dictionary.clone() for _ in range(a.dicts)]
+            copies = [dictionary.clone() for _ in range(a.dicts)]
             d_ptrs = torch.tensor([c.data_ptr() for c in copies], dtype=torch.int64, device="cuda")
             d_sizes = torch.tensor([c.numel() for c in copies], dtype=torch.int32, device="cuda")
-            states = torch.empty(a.dicts * state.numel(), dtype=torch.uint8, device="cuda")
+            one = state_hc if a.level >= 3 else state
+            set_prepare = L.lib.lz4mtHipDictSetPrepareHC if a.level >= 3 else L.lib.lz4mtHipDictSetPrepare
+            states = torch.empty(a.dicts * one.numel(), dtype=torch.uint8, device="cuda")
 
             def prepare_set():
-                r = L.lib.lz4mtHipDictSetPrepare(P(d_ptrs.data_ptr()), P(d_sizes.data_ptr()), a.dicts,
-                                                 P(states.data_ptr()), states.numel(), st)
+                r = set_prepare(P(d_ptrs.data_ptr()), P(d_sizes.data_ptr()), a.dicts, P(states.data_ptr()),
+                                states.numel(), st)
                 assert r == 0, r
 
             ps = timed(prepare_set, a.reps)
-            assert torch.equal(states.view(a.dicts, -1), state.view(1, -1).expand(a.dicts, -1))
+            assert torch.equal(states.view(a.dicts, -1), one.view(1, -1).expand(a.dicts, -1))
             prep.update({"dicts": a.dicts, "set_states_bytes": states.numel(),
                          "set_prepare_ms": round(ps[0], 4), "set_prepare_ms_min_max": [round(ps[1], 4), round(ps[2], 4)]})
-            dset = (d_ptrs, d_sizes, states, a.dicts)
+            dset = (d_ptrs, d_sizes, states, a.dicts, copies)
         dct = (dictionary, state, state_hc, dset)
     rows = []
     for name, k in (("4KiB", 4 << 10), ("64KiB", 64 << 10), ("1MiB", 1 << 20)):
