@@ -31,12 +31,31 @@ constexpr uint32_t kDictWindow = 64u << 10;
 constexpr uint32_t kDictHashUnit = 8;
 constexpr uint32_t kDictStateBytes = 16384 + 256;
 // the compressor's effective dictionary: the last min(dictSize, 64 KiB) bytes, none below HASH_UNIT
-inline uint32_t dict_effective(uint32_t dictSize) {
+__host__ __device__ inline uint32_t dict_effective(uint32_t dictSize) {
     return dictSize < kDictHashUnit ? 0u : (dictSize < kDictWindow ? dictSize : kDictWindow);
 }
-// A set of dictionaries with an index per chunk (section 5d): the index of a
-// chunk that has none (LZ4MT_HIP_BATCH_NO_DICT).
+// A set of dictionaries with an index per chunk (sections 5d, 5e): the index
+// of a chunk that has none (LZ4MT_HIP_BATCH_NO_DICT), and the size a set's
+// prepare records, where a state keeps its effective size, for a dictionary
+// that has a size and no pointer.  No effective size equals it, so the
+// encoders' guards refuse the chunks that name such a state.
 constexpr uint32_t kBatchNoDict = 0xFFFFFFFFu;
+constexpr uint32_t kDictStateBad = 0xFFFFFFFFu;
+static_assert(kDictStateBad > kDictWindow, "no effective size");
+
+// The launchers of the batched operators: n chunks (or dictionaries) in grids
+// of at most `grid`, launch(o, g) for the g items from o on; the first launch
+// error ends it.  kBatchGrid: the most workgroups these launchers put in a grid.
+constexpr uint32_t kBatchGrid = 1u << 30;
+template <class F>
+inline hipError_t launch_slices(uint32_t n, uint32_t grid, F&& launch) {
+    for (uint32_t o = 0, g; o < n; o += g) {
+        g = n - o < grid ? n - o : grid;
+        launch(o, g);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 
 #ifdef __HIP__
 // One chunk's descriptor, read at the uniform index blockIdx.x (scalar
@@ -150,8 +169,8 @@ hipError_t launch_encode_batch(const uint8_t* const* srcPtrs, const uint32_t* sr
                                hipStream_t st);
 hipError_t launch_decode_batch(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t nChunks,
                                uint8_t* const* dstPtrs, const uint32_t* dstCaps, int32_t* outSizes, hipStream_t st);
-// the same with a shared dictionary (k_dict_prepare, k_encode_batch_dict,
-// k_decode_batch_dict).  Encode: dictEnd is one past the dictionary's last
+// the same with a shared dictionary (k_dict_prepare,
+// k_encode_batch_dict<XC, SharedDict>, k_decode_batch_dict).  Encode: dictEnd is one past the dictionary's last
 // byte and D = dict_effective(dictSize) bytes before it are the dictionary;
 // state: kDictStateBytes, 256-byte aligned, written by launch_dict_prepare
 // for the same D.  Decode: the whole dictionary counts (dictSize bytes
@@ -165,7 +184,7 @@ hipError_t launch_decode_batch_dict(const uint8_t* const* srcPtrs, const uint32_
                                     uint8_t* const* dstPtrs, const uint32_t* dstCaps, int32_t* outSizes,
                                     const uint8_t* dictEnd, uint32_t dictSize, hipStream_t st);
 // the same with a set of dictionaries and an index per chunk (section 5d;
-// k_dict_set_prepare, k_encode_batch_dict_set, k_decode_batch_dict_set).
+// k_dict_set_prepare, k_encode_batch_dict<XC, DictSet>, k_decode_batch_dict_set).
 // dictPtrs / dictSizes / chunkDict are device arrays: the kernels compute the
 // dictionary's end and dict_effective themselves.  State k stands at states +
 // k * kDictStateBytes (256-byte aligned) and is what launch_dict_prepare
@@ -261,7 +280,8 @@ uint64_t hc_ws_bytes(uint64_t nBlocks, uint32_t blockSize, int level);   // spli
 uint32_t hc_attempts(int level);   // lz4hc nbSearches of a level (> 12 = 12)
 // The batched LZ4-HC (lz4mt_hip.h section 5, level >= 3): k_hc_prev_batch,
 // then k_encode_hc_batch (levels 3..9) or k_encode_hc_opt_batch (10 and up),
-// one wave per chunk.  Scratch comes in slots of hc_batch_slot_bytes(maxChunk,
+// one wave per chunk, each a template over the chunk's dictionary source
+// (here HcNoDict).  Scratch comes in slots of hc_batch_slot_bytes(maxChunk,
 // level): the chunk's chain deltas and, from level 10 up, its price table;
 // slot k serves the k-th chunk of a round.  ws holds `slots` >= 1 of them
 // (256-byte aligned); the batch runs in ceil(nChunks / slots) rounds over
@@ -274,8 +294,8 @@ uint64_t hc_batch_slot_bytes(uint32_t maxChunk, int level);
 hipError_t launch_encode_hc_batch(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
                                   uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps,
                                   int32_t* outSizes, int level, uint8_t* ws, uint32_t slots, hipStream_t st);
-// The same with a shared dictionary (section 5c; k_hc_dict_prepare,
-// k_hc_prev_batch_dict, k_encode_hc_batch_dict / k_encode_hc_opt_batch_dict).
+// The same with a shared dictionary (section 5c; k_hc_dict_prepare, the
+// batch kernels over HcSharedDict).
 // LZ4_loadDictHC keeps the last 64 KiB whatever their number (below 4 bytes
 // nothing is inserted, but the bytes still stand before the chunk).  The
 // prepared state serves every level; its layout is lz4mt_hc.hip's.
@@ -283,15 +303,16 @@ constexpr uint32_t kHcDictMagic = 0x4C7E4843u;
 constexpr uint32_t kHcDictHeadsAt = 16384 + 256;                       // behind the fast state's extent
 constexpr uint32_t kHcDictLinksAt = kHcDictHeadsAt + (4u << 15);
 constexpr uint32_t kHcDictStateBytes = kHcDictLinksAt + 2 * (kDictWindow + 128);
-inline uint32_t hc_dict_effective(uint32_t dictSize) { return dictSize < kDictWindow ? dictSize : kDictWindow; }
+__host__ __device__ inline uint32_t hc_dict_effective(uint32_t dictSize) {
+    return dictSize < kDictWindow ? dictSize : kDictWindow;
+}
 hipError_t launch_hc_dict_prepare(const uint8_t* dictEnd, uint32_t E, uint8_t* state, hipStream_t st);
 hipError_t launch_encode_hc_batch_dict(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
                                        uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps,
                                        int32_t* outSizes, const uint8_t* dictEnd, uint32_t E, const uint8_t* state,
                                        int level, uint8_t* ws, uint32_t slots, hipStream_t st);
 // The same with a set of dictionaries and an index per chunk (section 5e;
-// k_hc_dict_set_prepare, k_hc_prev_batch_dict_set, k_encode_hc_batch_dict_set /
-// k_encode_hc_opt_batch_dict_set).  dictPtrs / dictSizes / chunkDict are
+// k_hc_dict_set_prepare, the batch kernels over HcDictSet).  dictPtrs / dictSizes / chunkDict are
 // device arrays: the kernels compute the dictionary's end and its effective
 // size themselves.  State k stands at states + k * kHcDictStateBytes (256-byte
 // aligned) and is what launch_hc_dict_prepare writes for dictionary k.

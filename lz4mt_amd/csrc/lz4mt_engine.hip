@@ -540,17 +540,56 @@ extern "C" int lz4mtHipDecompressBlock(const char* src, char* dst, int isize, in
 // allocates, synchronises or reads the arrays, so a call can be captured
 // into a graph (the encoder-order check then behaves as for the frame
 // engine: launch_encode_batch -> encoder_path).
+// Every entry point decides in the same order: LZ4MT_RESULT_BAD_ARG from the
+// arguments alone, then LZ4MT_RESULT_ERROR without a device, then
+// LZ4MT_RESULT_OK for an empty batch, then the launch.
 static_assert(LZ4MT_HIP_BATCH_MAX_CHUNK == kBatchMaxChunk && LZ4MT_HIP_BATCH_BAD_CHUNK == kBatchBadChunk, "batch ABI");
+
+// The argument checks.  An empty batch (an empty set) needs none of its arrays.
+template <class... P>
+static bool arrays_given(uint32_t n, const P*... p) {
+    return n == 0 || (... && (p != nullptr));
+}
+// the chunk arrays of a compress call (d_dstCaps is optional) and its largest chunk
+static bool compress_chunks_ok(uint32_t nChunks, uint32_t maxChunkBytes, const void* const* srcPtrs,
+                               const uint32_t* srcSizes, void* const* dstPtrs, const int32_t* outSizes) {
+    return arrays_given(nChunks, srcPtrs, srcSizes, dstPtrs, outSizes) && maxChunkBytes <= LZ4MT_HIP_BATCH_MAX_CHUNK;
+}
+// the chunk arrays of a decompress call (d_dstCaps is required)
+static bool decompress_chunks_ok(uint32_t nChunks, const void* const* srcPtrs, const uint32_t* srcSizes,
+                                 void* const* dstPtrs, const uint32_t* dstCaps, const int32_t* outSizes) {
+    return arrays_given(nChunks, srcPtrs, srcSizes, dstPtrs, dstCaps, outSizes);
+}
+static bool dict_given(const void* d_dict, uint32_t dictSize) { return d_dict || dictSize == 0; }
+// a state, a set of states or a workspace: there, 256-byte aligned, of `need` bytes
+static bool buffer_ok(const void* p, uint64_t size = 0, uint64_t need = 0) {
+    return p && (reinterpret_cast<uintptr_t>(p) & 255) == 0 && size >= need;
+}
+// The slots of the caller's workspace that a batch at `level` uses
+// (launch_encode_hc_batch); 0: it does not hold one.
+static uint32_t hc_workspace_slots(uint32_t maxChunkBytes, int level, const void* d_workspace, uint64_t workspaceSize) {
+    const uint64_t slot = hc_batch_slot_bytes(maxChunkBytes, level);
+    if (!buffer_ok(d_workspace, workspaceSize, slot)) return 0;
+    return (uint32_t)std::min<uint64_t>(workspaceSize / slot, kHcBatchSlots);
+}
+
+// The ABI's untyped pointers as the launchers take them
+static const uint8_t* const* in_ptrs(const void* const* p) { return reinterpret_cast<const uint8_t* const*>(p); }
+static uint8_t* const* out_ptrs(void* const* p) { return reinterpret_cast<uint8_t* const*>(p); }
+static const uint8_t* dict_end(const void* d_dict, uint32_t dictSize) {
+    return static_cast<const uint8_t*>(d_dict) + dictSize;
+}
+static hipStream_t hip_stream(void* stream) { return static_cast<hipStream_t>(stream); }
+static Lz4MtResult launched(hipError_t e) { return e == hipSuccess ? LZ4MT_RESULT_OK : LZ4MT_RESULT_ERROR; }
+
 extern "C" Lz4MtResult lz4mtHipCompressBatch(const void* const* d_srcPtrs, const uint32_t* d_srcSizes,
                                              uint32_t maxChunkBytes, uint32_t nChunks, void* const* d_dstPtrs,
                                              const uint32_t* d_dstCaps, int32_t* d_outSizes, void* stream) {
-    if (nChunks && (!d_srcPtrs || !d_srcSizes || !d_dstPtrs || !d_outSizes)) return LZ4MT_RESULT_BAD_ARG;
-    if (maxChunkBytes > LZ4MT_HIP_BATCH_MAX_CHUNK) return LZ4MT_RESULT_BAD_ARG;
+    if (!compress_chunks_ok(nChunks, maxChunkBytes, d_srcPtrs, d_srcSizes, d_dstPtrs, d_outSizes))
+        return LZ4MT_RESULT_BAD_ARG;
     if (!have_device()) return LZ4MT_RESULT_ERROR;
-    HIPCHK(launch_encode_batch(reinterpret_cast<const uint8_t* const*>(d_srcPtrs), d_srcSizes, maxChunkBytes, nChunks,
-                               reinterpret_cast<uint8_t* const*>(d_dstPtrs), d_dstCaps, d_outSizes,
-                               static_cast<hipStream_t>(stream)));
-    return LZ4MT_RESULT_OK;
+    return launched(launch_encode_batch(in_ptrs(d_srcPtrs), d_srcSizes, maxChunkBytes, nChunks, out_ptrs(d_dstPtrs),
+                                        d_dstCaps, d_outSizes, hip_stream(stream)));
 }
 
 // The same with a level.  Below 3 it is lz4mtHipCompressBatch.  From 3 up:
@@ -570,29 +609,25 @@ extern "C" Lz4MtResult lz4mtHipCompressBatchEx(const void* const* d_srcPtrs, con
     if (level < 3)
         return lz4mtHipCompressBatch(d_srcPtrs, d_srcSizes, maxChunkBytes, nChunks, d_dstPtrs, d_dstCaps, d_outSizes,
                                      stream);
-    if (nChunks && (!d_srcPtrs || !d_srcSizes || !d_dstPtrs || !d_outSizes)) return LZ4MT_RESULT_BAD_ARG;
-    if (maxChunkBytes > LZ4MT_HIP_BATCH_MAX_CHUNK) return LZ4MT_RESULT_BAD_ARG;
-    const uint64_t slot = hc_batch_slot_bytes(maxChunkBytes, level);
-    if (nChunks && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0 || workspaceSize < slot))
+    if (!compress_chunks_ok(nChunks, maxChunkBytes, d_srcPtrs, d_srcSizes, d_dstPtrs, d_outSizes))
         return LZ4MT_RESULT_BAD_ARG;
+    const uint32_t slots = hc_workspace_slots(maxChunkBytes, level, d_workspace, workspaceSize);
+    if (nChunks && !slots) return LZ4MT_RESULT_BAD_ARG;
     if (!have_device()) return LZ4MT_RESULT_ERROR;
     if (nChunks == 0) return LZ4MT_RESULT_OK;
-    const uint32_t slots = (uint32_t)std::min<uint64_t>(workspaceSize / slot, kHcBatchSlots);
-    HIPCHK(launch_encode_hc_batch(reinterpret_cast<const uint8_t* const*>(d_srcPtrs), d_srcSizes, maxChunkBytes,
-                                  nChunks, reinterpret_cast<uint8_t* const*>(d_dstPtrs), d_dstCaps, d_outSizes, level,
-                                  static_cast<uint8_t*>(d_workspace), slots, static_cast<hipStream_t>(stream)));
-    return LZ4MT_RESULT_OK;
+    return launched(launch_encode_hc_batch(in_ptrs(d_srcPtrs), d_srcSizes, maxChunkBytes, nChunks, out_ptrs(d_dstPtrs),
+                                           d_dstCaps, d_outSizes, level, static_cast<uint8_t*>(d_workspace), slots,
+                                           hip_stream(stream)));
 }
 
 extern "C" Lz4MtResult lz4mtHipDecompressBatch(const void* const* d_srcPtrs, const uint32_t* d_srcSizes,
                                                uint32_t nChunks, void* const* d_dstPtrs, const uint32_t* d_dstCaps,
                                                int32_t* d_outSizes, void* stream) {
-    if (nChunks && (!d_srcPtrs || !d_srcSizes || !d_dstPtrs || !d_dstCaps || !d_outSizes)) return LZ4MT_RESULT_BAD_ARG;
+    if (!decompress_chunks_ok(nChunks, d_srcPtrs, d_srcSizes, d_dstPtrs, d_dstCaps, d_outSizes))
+        return LZ4MT_RESULT_BAD_ARG;
     if (!have_device()) return LZ4MT_RESULT_ERROR;
-    HIPCHK(launch_decode_batch(reinterpret_cast<const uint8_t* const*>(d_srcPtrs), d_srcSizes, nChunks,
-                               reinterpret_cast<uint8_t* const*>(d_dstPtrs), d_dstCaps, d_outSizes,
-                               static_cast<hipStream_t>(stream)));
-    return LZ4MT_RESULT_OK;
+    return launched(launch_decode_batch(in_ptrs(d_srcPtrs), d_srcSizes, nChunks, out_ptrs(d_dstPtrs), d_dstCaps,
+                                        d_outSizes, hip_stream(stream)));
 }
 
 // The batched operators with a shared dictionary (section 5b).  The host
@@ -601,55 +636,43 @@ extern "C" Lz4MtResult lz4mtHipDecompressBatch(const void* const* d_srcPtrs, con
 static_assert(LZ4MT_HIP_DICT_WINDOW == kDictWindow, "batch ABI");
 extern "C" uint64_t lz4mtHipDictStateSize(void) { return kDictStateBytes; }
 
-static bool dict_state_ok(const void* d_state, uint64_t stateSize) {
-    return d_state && (reinterpret_cast<uintptr_t>(d_state) & 255) == 0 && stateSize >= kDictStateBytes;
-}
-
 extern "C" Lz4MtResult lz4mtHipDictPrepare(const void* d_dict, uint32_t dictSize, void* d_state, uint64_t stateSize,
                                            void* stream) {
-    if (!d_dict && dictSize > 0) return LZ4MT_RESULT_BAD_ARG;
-    if (!dict_state_ok(d_state, stateSize)) return LZ4MT_RESULT_BAD_ARG;
+    if (!dict_given(d_dict, dictSize) || !buffer_ok(d_state, stateSize, kDictStateBytes)) return LZ4MT_RESULT_BAD_ARG;
     if (!have_device()) return LZ4MT_RESULT_ERROR;
-    HIPCHK(launch_dict_prepare(static_cast<const uint8_t*>(d_dict) + dictSize, dict_effective(dictSize),
-                               static_cast<uint32_t*>(d_state), static_cast<hipStream_t>(stream)));
-    return LZ4MT_RESULT_OK;
+    return launched(launch_dict_prepare(dict_end(d_dict, dictSize), dict_effective(dictSize),
+                                        static_cast<uint32_t*>(d_state), hip_stream(stream)));
 }
 
 extern "C" Lz4MtResult lz4mtHipCompressBatchDict(const void* const* d_srcPtrs, const uint32_t* d_srcSizes,
                                                  uint32_t maxChunkBytes, uint32_t nChunks, void* const* d_dstPtrs,
                                                  const uint32_t* d_dstCaps, int32_t* d_outSizes, const void* d_dict,
                                                  uint32_t dictSize, const void* d_state, void* stream) {
-    if (nChunks && (!d_srcPtrs || !d_srcSizes || !d_dstPtrs || !d_outSizes)) return LZ4MT_RESULT_BAD_ARG;
-    if (maxChunkBytes > LZ4MT_HIP_BATCH_MAX_CHUNK) return LZ4MT_RESULT_BAD_ARG;
-    if (!d_dict && dictSize > 0) return LZ4MT_RESULT_BAD_ARG;
-    if (!dict_state_ok(d_state, kDictStateBytes)) return LZ4MT_RESULT_BAD_ARG;
+    if (!compress_chunks_ok(nChunks, maxChunkBytes, d_srcPtrs, d_srcSizes, d_dstPtrs, d_outSizes) ||
+        !dict_given(d_dict, dictSize) || !buffer_ok(d_state))
+        return LZ4MT_RESULT_BAD_ARG;
     if (!have_device()) return LZ4MT_RESULT_ERROR;
     if (nChunks == 0) return LZ4MT_RESULT_OK;
-    HIPCHK(launch_encode_batch_dict(reinterpret_cast<const uint8_t* const*>(d_srcPtrs), d_srcSizes, maxChunkBytes,
-                                    nChunks, reinterpret_cast<uint8_t* const*>(d_dstPtrs), d_dstCaps, d_outSizes,
-                                    static_cast<const uint8_t*>(d_dict) + dictSize, dict_effective(dictSize),
-                                    static_cast<const uint32_t*>(d_state), static_cast<hipStream_t>(stream)));
-    return LZ4MT_RESULT_OK;
+    return launched(launch_encode_batch_dict(in_ptrs(d_srcPtrs), d_srcSizes, maxChunkBytes, nChunks,
+                                             out_ptrs(d_dstPtrs), d_dstCaps, d_outSizes, dict_end(d_dict, dictSize),
+                                             dict_effective(dictSize), static_cast<const uint32_t*>(d_state),
+                                             hip_stream(stream)));
 }
 
 extern "C" Lz4MtResult lz4mtHipDecompressBatchDict(const void* const* d_srcPtrs, const uint32_t* d_srcSizes,
                                                    uint32_t nChunks, void* const* d_dstPtrs,
                                                    const uint32_t* d_dstCaps, int32_t* d_outSizes, const void* d_dict,
                                                    uint32_t dictSize, void* stream) {
-    if (nChunks && (!d_srcPtrs || !d_srcSizes || !d_dstPtrs || !d_dstCaps || !d_outSizes)) return LZ4MT_RESULT_BAD_ARG;
-    if (!d_dict && dictSize > 0) return LZ4MT_RESULT_BAD_ARG;
+    if (!decompress_chunks_ok(nChunks, d_srcPtrs, d_srcSizes, d_dstPtrs, d_dstCaps, d_outSizes) ||
+        !dict_given(d_dict, dictSize))
+        return LZ4MT_RESULT_BAD_ARG;
     if (!have_device()) return LZ4MT_RESULT_ERROR;
     if (nChunks == 0) return LZ4MT_RESULT_OK;
     if (dictSize == 0)   // LZ4_decompress_safe_usingDict without a dictionary is LZ4_decompress_safe
-        HIPCHK(launch_decode_batch(reinterpret_cast<const uint8_t* const*>(d_srcPtrs), d_srcSizes, nChunks,
-                                   reinterpret_cast<uint8_t* const*>(d_dstPtrs), d_dstCaps, d_outSizes,
-                                   static_cast<hipStream_t>(stream)));
-    else
-        HIPCHK(launch_decode_batch_dict(reinterpret_cast<const uint8_t* const*>(d_srcPtrs), d_srcSizes, nChunks,
-                                        reinterpret_cast<uint8_t* const*>(d_dstPtrs), d_dstCaps, d_outSizes,
-                                        static_cast<const uint8_t*>(d_dict) + dictSize, dictSize,
-                                        static_cast<hipStream_t>(stream)));
-    return LZ4MT_RESULT_OK;
+        return launched(launch_decode_batch(in_ptrs(d_srcPtrs), d_srcSizes, nChunks, out_ptrs(d_dstPtrs), d_dstCaps,
+                                            d_outSizes, hip_stream(stream)));
+    return launched(launch_decode_batch_dict(in_ptrs(d_srcPtrs), d_srcSizes, nChunks, out_ptrs(d_dstPtrs), d_dstCaps,
+                                             d_outSizes, dict_end(d_dict, dictSize), dictSize, hip_stream(stream)));
 }
 
 // The same with a set of dictionaries and an index per chunk (section 5d).
@@ -658,15 +681,12 @@ extern "C" Lz4MtResult lz4mtHipDecompressBatchDict(const void* const* d_srcPtrs,
 static_assert(LZ4MT_HIP_BATCH_NO_DICT == kBatchNoDict, "batch ABI");
 extern "C" Lz4MtResult lz4mtHipDictSetPrepare(const void* const* d_dictPtrs, const uint32_t* d_dictSizes,
                                               uint32_t nDicts, void* d_states, uint64_t statesSize, void* stream) {
-    if (nDicts && (!d_dictPtrs || !d_dictSizes)) return LZ4MT_RESULT_BAD_ARG;
-    if (nDicts && (!d_states || (reinterpret_cast<uintptr_t>(d_states) & 255) != 0 ||
-                   statesSize < (uint64_t)nDicts * kDictStateBytes))
-        return LZ4MT_RESULT_BAD_ARG;
+    if (!arrays_given(nDicts, d_dictPtrs, d_dictSizes)) return LZ4MT_RESULT_BAD_ARG;
+    if (nDicts && !buffer_ok(d_states, statesSize, (uint64_t)nDicts * kDictStateBytes)) return LZ4MT_RESULT_BAD_ARG;
     if (!have_device()) return LZ4MT_RESULT_ERROR;
     if (nDicts == 0) return LZ4MT_RESULT_OK;
-    HIPCHK(launch_dict_set_prepare(reinterpret_cast<const uint8_t* const*>(d_dictPtrs), d_dictSizes, nDicts,
-                                   static_cast<uint32_t*>(d_states), static_cast<hipStream_t>(stream)));
-    return LZ4MT_RESULT_OK;
+    return launched(launch_dict_set_prepare(in_ptrs(d_dictPtrs), d_dictSizes, nDicts, static_cast<uint32_t*>(d_states),
+                                            hip_stream(stream)));
 }
 
 extern "C" Lz4MtResult lz4mtHipCompressBatchDictSet(const void* const* d_srcPtrs, const uint32_t* d_srcSizes,
@@ -675,19 +695,16 @@ extern "C" Lz4MtResult lz4mtHipCompressBatchDictSet(const void* const* d_srcPtrs
                                                     const void* const* d_dictPtrs, const uint32_t* d_dictSizes,
                                                     uint32_t nDicts, const void* d_states,
                                                     const uint32_t* d_chunkDict, void* stream) {
-    if (nChunks && (!d_srcPtrs || !d_srcSizes || !d_dstPtrs || !d_outSizes || !d_chunkDict))
+    if (!compress_chunks_ok(nChunks, maxChunkBytes, d_srcPtrs, d_srcSizes, d_dstPtrs, d_outSizes) ||
+        !arrays_given(nChunks, d_chunkDict) || !arrays_given(nDicts, d_dictPtrs, d_dictSizes) ||
+        (nDicts && !buffer_ok(d_states)))
         return LZ4MT_RESULT_BAD_ARG;
-    if (maxChunkBytes > LZ4MT_HIP_BATCH_MAX_CHUNK) return LZ4MT_RESULT_BAD_ARG;
-    if (nDicts && (!d_dictPtrs || !d_dictSizes)) return LZ4MT_RESULT_BAD_ARG;
-    if (nDicts && (!d_states || (reinterpret_cast<uintptr_t>(d_states) & 255) != 0)) return LZ4MT_RESULT_BAD_ARG;
     if (!have_device()) return LZ4MT_RESULT_ERROR;
     if (nChunks == 0) return LZ4MT_RESULT_OK;
-    HIPCHK(launch_encode_batch_dict_set(reinterpret_cast<const uint8_t* const*>(d_srcPtrs), d_srcSizes, maxChunkBytes,
-                                        nChunks, reinterpret_cast<uint8_t* const*>(d_dstPtrs), d_dstCaps, d_outSizes,
-                                        reinterpret_cast<const uint8_t* const*>(d_dictPtrs), d_dictSizes, nDicts,
-                                        static_cast<const uint32_t*>(d_states), d_chunkDict,
-                                        static_cast<hipStream_t>(stream)));
-    return LZ4MT_RESULT_OK;
+    return launched(launch_encode_batch_dict_set(in_ptrs(d_srcPtrs), d_srcSizes, maxChunkBytes, nChunks,
+                                                 out_ptrs(d_dstPtrs), d_dstCaps, d_outSizes, in_ptrs(d_dictPtrs),
+                                                 d_dictSizes, nDicts, static_cast<const uint32_t*>(d_states),
+                                                 d_chunkDict, hip_stream(stream)));
 }
 
 extern "C" Lz4MtResult lz4mtHipDecompressBatchDictSet(const void* const* d_srcPtrs, const uint32_t* d_srcSizes,
@@ -695,16 +712,14 @@ extern "C" Lz4MtResult lz4mtHipDecompressBatchDictSet(const void* const* d_srcPt
                                                       const uint32_t* d_dstCaps, int32_t* d_outSizes,
                                                       const void* const* d_dictPtrs, const uint32_t* d_dictSizes,
                                                       uint32_t nDicts, const uint32_t* d_chunkDict, void* stream) {
-    if (nChunks && (!d_srcPtrs || !d_srcSizes || !d_dstPtrs || !d_dstCaps || !d_outSizes || !d_chunkDict))
+    if (!decompress_chunks_ok(nChunks, d_srcPtrs, d_srcSizes, d_dstPtrs, d_dstCaps, d_outSizes) ||
+        !arrays_given(nChunks, d_chunkDict) || !arrays_given(nDicts, d_dictPtrs, d_dictSizes))
         return LZ4MT_RESULT_BAD_ARG;
-    if (nDicts && (!d_dictPtrs || !d_dictSizes)) return LZ4MT_RESULT_BAD_ARG;
     if (!have_device()) return LZ4MT_RESULT_ERROR;
     if (nChunks == 0) return LZ4MT_RESULT_OK;
-    HIPCHK(launch_decode_batch_dict_set(reinterpret_cast<const uint8_t* const*>(d_srcPtrs), d_srcSizes, nChunks,
-                                        reinterpret_cast<uint8_t* const*>(d_dstPtrs), d_dstCaps, d_outSizes,
-                                        reinterpret_cast<const uint8_t* const*>(d_dictPtrs), d_dictSizes, nDicts,
-                                        d_chunkDict, static_cast<hipStream_t>(stream)));
-    return LZ4MT_RESULT_OK;
+    return launched(launch_decode_batch_dict_set(in_ptrs(d_srcPtrs), d_srcSizes, nChunks, out_ptrs(d_dstPtrs),
+                                                 d_dstCaps, d_outSizes, in_ptrs(d_dictPtrs), d_dictSizes, nDicts,
+                                                 d_chunkDict, hip_stream(stream)));
 }
 
 // LZ4-HC with a shared dictionary (section 5c).  As above the host only trims
@@ -713,13 +728,11 @@ extern "C" uint64_t lz4mtHipDictStateSizeHC(void) { return kHcDictStateBytes; }
 
 extern "C" Lz4MtResult lz4mtHipDictPrepareHC(const void* d_dict, uint32_t dictSize, void* d_state, uint64_t stateSize,
                                              void* stream) {
-    if (!d_dict && dictSize > 0) return LZ4MT_RESULT_BAD_ARG;
-    if (!d_state || (reinterpret_cast<uintptr_t>(d_state) & 255) != 0 || stateSize < kHcDictStateBytes)
+    if (!dict_given(d_dict, dictSize) || !buffer_ok(d_state, stateSize, kHcDictStateBytes))
         return LZ4MT_RESULT_BAD_ARG;
     if (!have_device()) return LZ4MT_RESULT_ERROR;
-    HIPCHK(launch_hc_dict_prepare(static_cast<const uint8_t*>(d_dict) + dictSize, hc_dict_effective(dictSize),
-                                  static_cast<uint8_t*>(d_state), static_cast<hipStream_t>(stream)));
-    return LZ4MT_RESULT_OK;
+    return launched(launch_hc_dict_prepare(dict_end(d_dict, dictSize), hc_dict_effective(dictSize),
+                                           static_cast<uint8_t*>(d_state), hip_stream(stream)));
 }
 
 extern "C" uint64_t lz4mtHipCompressBatchDictWorkspaceSize(uint32_t maxChunkBytes, uint32_t nChunks, int level) {
@@ -731,23 +744,17 @@ extern "C" Lz4MtResult lz4mtHipCompressBatchDictHC(const void* const* d_srcPtrs,
                                                    const uint32_t* d_dstCaps, int32_t* d_outSizes, const void* d_dict,
                                                    uint32_t dictSize, const void* d_stateHC, int level,
                                                    void* d_workspace, uint64_t workspaceSize, void* stream) {
-    if (nChunks && (!d_srcPtrs || !d_srcSizes || !d_dstPtrs || !d_outSizes)) return LZ4MT_RESULT_BAD_ARG;
-    if (maxChunkBytes > LZ4MT_HIP_BATCH_MAX_CHUNK) return LZ4MT_RESULT_BAD_ARG;
-    if (level < 3) return LZ4MT_RESULT_BAD_ARG;
-    if (!d_dict && dictSize > 0) return LZ4MT_RESULT_BAD_ARG;
-    if (!d_stateHC || (reinterpret_cast<uintptr_t>(d_stateHC) & 255) != 0) return LZ4MT_RESULT_BAD_ARG;
-    const uint64_t slot = hc_batch_slot_bytes(maxChunkBytes, level);
-    if (nChunks && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0 || workspaceSize < slot))
+    if (!compress_chunks_ok(nChunks, maxChunkBytes, d_srcPtrs, d_srcSizes, d_dstPtrs, d_outSizes) || level < 3 ||
+        !dict_given(d_dict, dictSize) || !buffer_ok(d_stateHC))
         return LZ4MT_RESULT_BAD_ARG;
+    const uint32_t slots = hc_workspace_slots(maxChunkBytes, level, d_workspace, workspaceSize);
+    if (nChunks && !slots) return LZ4MT_RESULT_BAD_ARG;
     if (!have_device()) return LZ4MT_RESULT_ERROR;
     if (nChunks == 0) return LZ4MT_RESULT_OK;
-    const uint32_t slots = (uint32_t)std::min<uint64_t>(workspaceSize / slot, kHcBatchSlots);
-    HIPCHK(launch_encode_hc_batch_dict(reinterpret_cast<const uint8_t* const*>(d_srcPtrs), d_srcSizes, maxChunkBytes,
-                                       nChunks, reinterpret_cast<uint8_t* const*>(d_dstPtrs), d_dstCaps, d_outSizes,
-                                       static_cast<const uint8_t*>(d_dict) + dictSize, hc_dict_effective(dictSize),
-                                       static_cast<const uint8_t*>(d_stateHC), level,
-                                       static_cast<uint8_t*>(d_workspace), slots, static_cast<hipStream_t>(stream)));
-    return LZ4MT_RESULT_OK;
+    return launched(launch_encode_hc_batch_dict(in_ptrs(d_srcPtrs), d_srcSizes, maxChunkBytes, nChunks,
+                                                out_ptrs(d_dstPtrs), d_dstCaps, d_outSizes, dict_end(d_dict, dictSize),
+                                                hc_dict_effective(dictSize), static_cast<const uint8_t*>(d_stateHC),
+                                                level, static_cast<uint8_t*>(d_workspace), slots, hip_stream(stream)));
 }
 
 // LZ4-HC with a set of dictionaries and an index per chunk (section 5e).  The
@@ -756,15 +763,12 @@ extern "C" Lz4MtResult lz4mtHipCompressBatchDictHC(const void* const* d_srcPtrs,
 extern "C" Lz4MtResult lz4mtHipDictSetPrepareHC(const void* const* d_dictPtrs, const uint32_t* d_dictSizes,
                                                 uint32_t nDicts, void* d_statesHC, uint64_t statesSize,
                                                 void* stream) {
-    if (nDicts && (!d_dictPtrs || !d_dictSizes)) return LZ4MT_RESULT_BAD_ARG;
-    if (nDicts && (!d_statesHC || (reinterpret_cast<uintptr_t>(d_statesHC) & 255) != 0 ||
-                   statesSize < (uint64_t)nDicts * kHcDictStateBytes))
-        return LZ4MT_RESULT_BAD_ARG;
+    if (!arrays_given(nDicts, d_dictPtrs, d_dictSizes)) return LZ4MT_RESULT_BAD_ARG;
+    if (nDicts && !buffer_ok(d_statesHC, statesSize, (uint64_t)nDicts * kHcDictStateBytes)) return LZ4MT_RESULT_BAD_ARG;
     if (!have_device()) return LZ4MT_RESULT_ERROR;
     if (nDicts == 0) return LZ4MT_RESULT_OK;
-    HIPCHK(launch_hc_dict_set_prepare(reinterpret_cast<const uint8_t* const*>(d_dictPtrs), d_dictSizes, nDicts,
-                                      static_cast<uint8_t*>(d_statesHC), static_cast<hipStream_t>(stream)));
-    return LZ4MT_RESULT_OK;
+    return launched(launch_hc_dict_set_prepare(in_ptrs(d_dictPtrs), d_dictSizes, nDicts,
+                                               static_cast<uint8_t*>(d_statesHC), hip_stream(stream)));
 }
 
 extern "C" Lz4MtResult lz4mtHipCompressBatchDictSetHC(const void* const* d_srcPtrs, const uint32_t* d_srcSizes,
@@ -774,25 +778,18 @@ extern "C" Lz4MtResult lz4mtHipCompressBatchDictSetHC(const void* const* d_srcPt
                                                       const uint32_t* d_dictSizes, uint32_t nDicts,
                                                       const void* d_statesHC, const uint32_t* d_chunkDict, int level,
                                                       void* d_workspace, uint64_t workspaceSize, void* stream) {
-    if (nChunks && (!d_srcPtrs || !d_srcSizes || !d_dstPtrs || !d_outSizes || !d_chunkDict))
+    if (!compress_chunks_ok(nChunks, maxChunkBytes, d_srcPtrs, d_srcSizes, d_dstPtrs, d_outSizes) ||
+        !arrays_given(nChunks, d_chunkDict) || level < 3 || !arrays_given(nDicts, d_dictPtrs, d_dictSizes) ||
+        (nDicts && !buffer_ok(d_statesHC)))
         return LZ4MT_RESULT_BAD_ARG;
-    if (maxChunkBytes > LZ4MT_HIP_BATCH_MAX_CHUNK) return LZ4MT_RESULT_BAD_ARG;
-    if (level < 3) return LZ4MT_RESULT_BAD_ARG;
-    if (nDicts && (!d_dictPtrs || !d_dictSizes)) return LZ4MT_RESULT_BAD_ARG;
-    if (nDicts && (!d_statesHC || (reinterpret_cast<uintptr_t>(d_statesHC) & 255) != 0)) return LZ4MT_RESULT_BAD_ARG;
-    const uint64_t slot = hc_batch_slot_bytes(maxChunkBytes, level);
-    if (nChunks && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 255) != 0 || workspaceSize < slot))
-        return LZ4MT_RESULT_BAD_ARG;
+    const uint32_t slots = hc_workspace_slots(maxChunkBytes, level, d_workspace, workspaceSize);
+    if (nChunks && !slots) return LZ4MT_RESULT_BAD_ARG;
     if (!have_device()) return LZ4MT_RESULT_ERROR;
     if (nChunks == 0) return LZ4MT_RESULT_OK;
-    const uint32_t slots = (uint32_t)std::min<uint64_t>(workspaceSize / slot, kHcBatchSlots);
-    HIPCHK(launch_encode_hc_batch_dict_set(
-        reinterpret_cast<const uint8_t* const*>(d_srcPtrs), d_srcSizes, maxChunkBytes, nChunks,
-        reinterpret_cast<uint8_t* const*>(d_dstPtrs), d_dstCaps, d_outSizes,
-        reinterpret_cast<const uint8_t* const*>(d_dictPtrs), d_dictSizes, nDicts,
-        static_cast<const uint8_t*>(d_statesHC), d_chunkDict, level, static_cast<uint8_t*>(d_workspace), slots,
-        static_cast<hipStream_t>(stream)));
-    return LZ4MT_RESULT_OK;
+    return launched(launch_encode_hc_batch_dict_set(
+        in_ptrs(d_srcPtrs), d_srcSizes, maxChunkBytes, nChunks, out_ptrs(d_dstPtrs), d_dstCaps, d_outSizes,
+        in_ptrs(d_dictPtrs), d_dictSizes, nDicts, static_cast<const uint8_t*>(d_statesHC), d_chunkDict, level,
+        static_cast<uint8_t*>(d_workspace), slots, hip_stream(stream)));
 }
 
 // ===========================================================================

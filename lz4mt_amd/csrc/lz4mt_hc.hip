@@ -397,7 +397,7 @@ struct HcBlock {
 // lowLimit = 0, dictLimit = E here).  The parsers work in chunk offsets; a
 // match position leaves wider() minus E (wrapping below 0 for one in the
 // dictionary), so `ip - ref` is its offset either way.
-//   dl   the chunk's deltas (k_hc_prev_batch_dict: distance in positions, so a
+//   dl   the chunk's deltas (k_hc_prev_batch behind a dictionary: distance in positions, so a
 //        link may reach into the dictionary; 0 = none within 65535)
 //   ddl  the dictionary's links as lz4hc's chainTable holds them (65535 =
 //        none, 0 = never inserted: its last three positions)
@@ -1133,67 +1133,15 @@ __global__ void __launch_bounds__(64) k_encode_hc_opt_g(const uint8_t* __restric
 // therefore never used.
 // As in k_encode_batch: no wait on another wave, no loop over chunks, no
 // atomics: a wave (a workgroup of k_hc_prev_batch) that runs ends.
+// The three kernels are templates over the chunk's dictionary source (below).
 // ---------------------------------------------------------------------------
 constexpr uint64_t kHcBatchDeltaPad = 128;   // bytes after a slot's maxChunk deltas (64 entries)
 constexpr uint64_t hc_batch_delta_bytes(uint32_t maxChunk) {
     return (2 * (uint64_t)maxChunk + kHcBatchDeltaPad + 255) & ~uint64_t(255);
 }
 
-// The chain of every chunk of the round, one workgroup per chunk.  The
-// refusal is workgroup-uniform (blockIdx.x only) and comes before the first
-// __syncthreads; hc_prev_range's early end for n < 4 is uniform as well.
-__global__ void __launch_bounds__(kPrevThreads) k_hc_prev_batch(const uint8_t* const* __restrict__ srcPtrs,
-                                                                const uint32_t* __restrict__ srcSizes,
-                                                                uint32_t maxChunk,
-                                                                uint8_t* const* __restrict__ dstPtrs,
-                                                                uint8_t* __restrict__ ws, uint64_t slotBytes) {
-    __shared__ uint32_t last[1u << kHashLog];
-    __shared__ uint8_t dd[4 * 1024];
-    __shared__ __attribute__((aligned(16))) uint32_t ring[2048];
-    const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, nullptr);
-    if (c.bad) return;   // a size above maxChunk would not fit the slot
-    hc_prev_range(c.s, c.n, (g_u16*)(ws + (uint64_t)blockIdx.x * slotBytes), (l_u32*)last, (l_u8*)dd, (l_u32*)ring);
-}
-
-// Levels 3..9: the hashChain parse of chunk blockIdx.x, one wave
-__global__ void __launch_bounds__(64) k_encode_hc_batch(const uint8_t* const* __restrict__ srcPtrs,
-                                                        const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
-                                                        uint8_t* const* __restrict__ dstPtrs,
-                                                        const uint32_t* __restrict__ dstCaps,
-                                                        int32_t* __restrict__ outSizes,
-                                                        const uint8_t* __restrict__ ws, uint64_t slotBytes,
-                                                        uint32_t maxAttempts) {
-    const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, dstCaps);
-    int32_t r = kBatchBadChunk;
-    if (!c.bad) {
-        HcBlock B{c.s, c.n, (g_cu16*)(ws + (uint64_t)blockIdx.x * slotBytes), maxAttempts, maxAttempts > 128};
-        r = encode_block_hc(B, c.d, c.cap);
-    }
-    if (laneid() == 0) outSizes[blockIdx.x] = r;
-}
-
-// Levels 10..12: the optimal parse of chunk blockIdx.x, one wave, the price
-// table after the slot's deltas (global memory, as k_encode_hc_opt_g's)
-__global__ void __launch_bounds__(64) k_encode_hc_opt_batch(const uint8_t* const* __restrict__ srcPtrs,
-                                                            const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
-                                                            uint8_t* const* __restrict__ dstPtrs,
-                                                            const uint32_t* __restrict__ dstCaps,
-                                                            int32_t* __restrict__ outSizes, uint8_t* ws,
-                                                            uint64_t slotBytes, uint64_t tableAt, uint32_t nbSearches,
-                                                            int32_t sufficientLen, int32_t fullUpdate) {
-    const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, dstCaps);
-    int32_t r = kBatchBadChunk;
-    if (!c.bad) {
-        uint8_t* slot = ws + (uint64_t)blockIdx.x * slotBytes;
-        HcBlock B{c.s, c.n, (g_cu16*)slot, nbSearches, true};   // pattern analysis always on
-        r = encode_block_hc_opt(B, c.d, c.cap, hc_opt_at(slot + tableAt, 0), sufficientLen, fullUpdate != 0);
-    }
-    if (laneid() == 0) outSizes[blockIdx.x] = r;
-}
-
 // ---------------------------------------------------------------------------
-// The same with a shared dictionary (lz4mt_hip.h section 5c,
-// lz4mtHipDictPrepareHC / lz4mtHipCompressBatchDictHC): every chunk is
+// With a dictionary (lz4mt_hip.h sections 5c and 5e): every chunk is
 // LZ4_loadDictHC(dict) + LZ4_compress_HC_continue(chunk) on a fresh stream,
 // the dictionary in a buffer of its own (HcDictBlock).
 // The state (kHcDictStateBytes, 256-byte aligned), level-independent:
@@ -1215,232 +1163,218 @@ static_assert(kHcDictHeadsAt % 16 == 0 && kHcDictLinksAt == kHcDictHeadsAt + (4u
               kHcDictStateBytes == kHcDictLinksAt + 2 * (kDictWindow + 128) && kHcDictStateBytes % 256 == 0 &&
               kHcDictHeadsAt > 4096 * 4 + 4, "HC dictionary state");
 
+// The one guard of a state: an HC state built for the effective size E (the
+// size word first: two instructions fewer in k_hc_prev_batch<HcSharedDict>)
 __device__ __forceinline__ bool hc_dict_state_ok(const uint8_t* state, uint32_t E) {
     const uint32_t* w = (const uint32_t*)state;
-    return w[0] == kHcDictMagic && w[1] == E;
+    return w[1] == E && w[0] == kHcDictMagic;
 }
 
-// One workgroup: hc_prev_range over the effective dictionary [dictEnd - E,
-// dictEnd) (read by bytes, or by aligned 16 bytes inside it: nothing outside
-// is read), then the heads and the rest of the state.  Every word of the
-// state is written, each by one thread.
-__global__ void __launch_bounds__(kPrevThreads) k_hc_dict_prepare(const uint8_t* __restrict__ dictEnd, uint32_t E,
-                                                                  uint8_t* __restrict__ state) {
-    __shared__ uint32_t last[1u << kHashLog];
-    __shared__ uint8_t dd[4 * 1024];
-    __shared__ __attribute__((aligned(16))) uint32_t ring[2048];
+// The state of one dictionary, by one workgroup: hc_prev_range over the
+// effective dictionary [dictEnd - E, dictEnd) (read by bytes, or by aligned
+// 16 bytes inside it: nothing outside is read), then the heads and the rest
+// of the state.  Every word of the state is written, each by one thread.
+// `recorded` is what word 1 keeps: E, or kDictStateBad (lz4mt_device.h).
+__device__ __forceinline__ void hc_dict_prepare(const uint8_t* dictEnd, uint32_t E, uint32_t recorded, uint8_t* state,
+                                                l_u32* last, l_u8* dd, l_u32* ring) {
     const uint32_t t = threadIdx.x;
     g_u16* links = (g_u16*)(state + kHcDictLinksAt);
-    hc_prev_range<kPrevDict>((g_cu8*)dictEnd - E, E, links, (l_u32*)last, (l_u8*)dd, (l_u32*)ring);
+    hc_prev_range<kPrevDict>((g_cu8*)dictEnd - E, E, links, last, dd, ring);
     __syncthreads();
     uint32_t* heads = (uint32_t*)(state + kHcDictHeadsAt);
     for (uint32_t i = t; i < (1u << kHashLog); i += kPrevThreads) heads[i] = last[i];
     for (uint32_t p = (E >= 4 ? E - 3 : 0u) + t; p < kDictWindow + 128; p += kPrevThreads) links[p] = 0;
     uint32_t* w = (uint32_t*)state;
     for (uint32_t i = t; i < kHcDictHeadsAt / 4; i += kPrevThreads)
-        w[i] = i == 0 ? kHcDictMagic : i == 1 ? E : i == 4096 ? 0xFFFFFFFFu : 0u;
+        w[i] = i == 0 ? kHcDictMagic : i == 1 ? recorded : i == 4096 ? 0xFFFFFFFFu : 0u;
 }
 
-// The chain of every chunk of the round behind the dictionary.  A state that
-// is not an HC state for E ends the workgroup (uniform, before any barrier):
-// the parse kernel refuses the chunk.
-__global__ void __launch_bounds__(kPrevThreads) k_hc_prev_batch_dict(const uint8_t* const* __restrict__ srcPtrs,
-                                                                     const uint32_t* __restrict__ srcSizes,
-                                                                     uint32_t maxChunk,
-                                                                     uint8_t* const* __restrict__ dstPtrs,
-                                                                     uint8_t* __restrict__ ws, uint64_t slotBytes,
-                                                                     const uint8_t* __restrict__ state, uint32_t E) {
+__global__ void __launch_bounds__(kPrevThreads) k_hc_dict_prepare(const uint8_t* __restrict__ dictEnd, uint32_t E,
+                                                                  uint8_t* __restrict__ state) {
     __shared__ uint32_t last[1u << kHashLog];
     __shared__ uint8_t dd[4 * 1024];
     __shared__ __attribute__((aligned(16))) uint32_t ring[2048];
-    const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, nullptr);
-    if (c.bad || !hc_dict_state_ok(state, E)) return;
-    hc_prev_range<kPrevChunk>(c.s, c.n, (g_u16*)(ws + (uint64_t)blockIdx.x * slotBytes), (l_u32*)last, (l_u8*)dd,
-                              (l_u32*)ring, (const uint32_t*)(state + kHcDictHeadsAt), E);
+    hc_dict_prepare(dictEnd, E, E, state, (l_u32*)last, (l_u8*)dd, (l_u32*)ring);
 }
 
-__device__ __forceinline__ HcDictBlock hc_dict_block(const BatchChunk& c, const uint8_t* slot, const uint8_t* dictEnd,
-                                                     uint32_t E, const uint8_t* state, uint32_t attempts,
-                                                     bool pattern) {
-    return HcDictBlock{c.s, c.n, (g_cu16*)slot, (g_cu8*)dictEnd - E, (g_cu16*)(state + kHcDictLinksAt), E, attempts,
-                       pattern};
-}
-
-// Levels 3..9 / 10..12: k_encode_hc_batch / k_encode_hc_opt_batch over HcDictBlock
-__global__ void __launch_bounds__(64) k_encode_hc_batch_dict(const uint8_t* const* __restrict__ srcPtrs,
-                                                             const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
-                                                             uint8_t* const* __restrict__ dstPtrs,
-                                                             const uint32_t* __restrict__ dstCaps,
-                                                             int32_t* __restrict__ outSizes,
-                                                             const uint8_t* __restrict__ ws, uint64_t slotBytes,
-                                                             uint32_t maxAttempts, const uint8_t* __restrict__ dictEnd,
-                                                             uint32_t E, const uint8_t* __restrict__ state) {
-    const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, dstCaps);
-    int32_t r = kBatchBadChunk;
-    if (!c.bad && hc_dict_state_ok(state, E)) {
-        const HcDictBlock B =
-            hc_dict_block(c, ws + (uint64_t)blockIdx.x * slotBytes, dictEnd, E, state, maxAttempts, maxAttempts > 128);
-        r = encode_block_hc(B, c.d, c.cap);
-    }
-    if (laneid() == 0) outSizes[blockIdx.x] = r;
-}
-
-__global__ void __launch_bounds__(64) k_encode_hc_opt_batch_dict(const uint8_t* const* __restrict__ srcPtrs,
-                                                                 const uint32_t* __restrict__ srcSizes,
-                                                                 uint32_t maxChunk, uint8_t* const* __restrict__ dstPtrs,
-                                                                 const uint32_t* __restrict__ dstCaps,
-                                                                 int32_t* __restrict__ outSizes, uint8_t* ws,
-                                                                 uint64_t slotBytes, uint64_t tableAt,
-                                                                 uint32_t nbSearches, int32_t sufficientLen,
-                                                                 int32_t fullUpdate, const uint8_t* __restrict__ dictEnd,
-                                                                 uint32_t E, const uint8_t* __restrict__ state) {
-    const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, dstCaps);
-    int32_t r = kBatchBadChunk;
-    if (!c.bad && hc_dict_state_ok(state, E)) {
-        uint8_t* slot = ws + (uint64_t)blockIdx.x * slotBytes;
-        const HcDictBlock B = hc_dict_block(c, slot, dictEnd, E, state, nbSearches, true);
-        r = encode_block_hc_opt(B, c.d, c.cap, hc_opt_at(slot + tableAt, 0), sufficientLen, fullUpdate != 0);
-    }
-    if (laneid() == 0) outSizes[blockIdx.x] = r;
-}
-
-// ---------------------------------------------------------------------------
-// The same with a set of dictionaries and an index per chunk (lz4mt_hip.h
-// section 5e, lz4mtHipDictSetPrepareHC / lz4mtHipCompressBatchDictSetHC).
-// The dictionaries' pointers and sizes are device arrays, so what the host
-// does for section 5c happens here: E = min(size, 64 KiB) and the
-// dictionary's end, pointer + size in 64-bit arithmetic.  State k stands
-// kHcDictStateBytes behind state k - 1 and is byte for byte what
-// k_hc_dict_prepare writes for dictionary k.
-// kHcDictStateBad: the recorded size of a dictionary that has a size and no
-// pointer.  No effective size equals it, so hc_dict_state_ok refuses it for
-// every dictionary.
-// kBatchNoDict is served as an HcDictBlock with E = 0 behind a chain built
-// from an empty table (kPrevPlain: the deltas k_hc_prev_batch writes): no
-// position lies below E, so neither `dict` nor `ddl` is ever read, and the
-// parse writes lz4mtHipCompressBatchEx's bytes (section 5c's E < 4 rule,
-// pinned by the fixture's 0-byte dictionary).  It needs no state.
-// ---------------------------------------------------------------------------
-constexpr uint32_t kHcDictStateBad = 0xFFFFFFFFu;
-static_assert(kHcDictStateBad > kDictWindow, "no effective size");
-
-// k_hc_dict_prepare's work, workgroup k for dictionary k (pointer and size are
-// uniform scalar loads).  A dictionary with a size and no pointer is treated
-// as empty and recorded as kHcDictStateBad.
+// Workgroup k for dictionary k of a set (section 5e; pointer and size are
+// uniform scalar loads): what the host does for section 5c happens here, E
+// and the dictionary's end, pointer + size in 64-bit arithmetic.  State k
+// stands kHcDictStateBytes behind state k - 1.  A dictionary with a size and
+// no pointer is treated as empty and recorded as kDictStateBad: no effective
+// size equals it, so hc_dict_state_ok refuses it for every dictionary.
 __global__ void __launch_bounds__(kPrevThreads) k_hc_dict_set_prepare(const uint8_t* const* __restrict__ dictPtrs,
                                                                       const uint32_t* __restrict__ dictSizes,
                                                                       uint8_t* __restrict__ states) {
     __shared__ uint32_t last[1u << kHashLog];
     __shared__ uint8_t dd[4 * 1024];
     __shared__ __attribute__((aligned(16))) uint32_t ring[2048];
-    const uint32_t t = threadIdx.x, k = blockIdx.x;
-    const uint32_t size = dictSizes[k];
+    const uint32_t k = blockIdx.x, size = dictSizes[k];
     const uint8_t* dp = dictPtrs[k];
     const bool bad = !dp && size != 0;
-    const uint32_t E = bad ? 0u : (size < kDictWindow ? size : kDictWindow);
-    const uint8_t* dictEnd = dp + size;
-    uint8_t* state = states + (uint64_t)k * kHcDictStateBytes;
-    g_u16* links = (g_u16*)(state + kHcDictLinksAt);
-    hc_prev_range<kPrevDict>((g_cu8*)dictEnd - E, E, links, (l_u32*)last, (l_u8*)dd, (l_u32*)ring);
-    __syncthreads();
-    uint32_t* heads = (uint32_t*)(state + kHcDictHeadsAt);
-    for (uint32_t i = t; i < (1u << kHashLog); i += kPrevThreads) heads[i] = last[i];
-    for (uint32_t p = (E >= 4 ? E - 3 : 0u) + t; p < kDictWindow + 128; p += kPrevThreads) links[p] = 0;
-    uint32_t* w = (uint32_t*)state;
-    for (uint32_t i = t; i < kHcDictHeadsAt / 4; i += kPrevThreads)
-        w[i] = i == 0 ? kHcDictMagic : i == 1 ? (bad ? kHcDictStateBad : E) : i == 4096 ? 0xFFFFFFFFu : 0u;
+    const uint32_t E = bad ? 0u : hc_dict_effective(size);
+    hc_dict_prepare(dp + size, E, bad ? kDictStateBad : E, states + (uint64_t)k * kHcDictStateBytes, (l_u32*)last,
+                    (l_u8*)dd, (l_u32*)ring);
 }
 
-// The dictionary of chunk blockIdx.x (all uniform: scalar loads).  ok: the
-// chunk has no dictionary (state == nullptr, E = 0), or names dictionary k <
-// nDicts that has a pointer or no size and whose state k is an HC state for
-// its effective size.  The one place the chain kernel and the parse kernels
-// take a dictionary's refusal from, so a parse wave never reads a slot whose
-// chain was not written for it in this round.
-struct HcSetDict {
-    const uint8_t* dictEnd;
-    const uint8_t* state;   // nullptr: no dictionary
-    uint32_t E;
-    bool ok;
+// ---------------------------------------------------------------------------
+// Dictionary sources.  A batch kernel takes one by value and asks it, for
+// chunk blockIdx.x (every answer uniform: scalar loads):
+//   chunk()   the chunk's dictionary: dictEnd, E and state (heads at
+//             kHcDictHeadsAt, links at kHcDictLinksAt), and
+//   ok()      false: the chunk is refused (LZ4MT_HIP_BATCH_BAD_CHUNK);
+//   has()     false: the chunk has no dictionary.
+// ok() is the one place the chain kernel and the parse kernels take a
+// dictionary's refusal from, so a parse wave never reads a slot whose chain
+// was not written for it in this round.  A new variant of the batch (another
+// way to name a chunk's dictionary) is a new source type, not new kernels.
+// On the host: given() (the launcher's argument check) and from(o), the
+// source of a round that starts at chunk o.
+// ---------------------------------------------------------------------------
+// lz4mtHipCompressBatchEx: no dictionary; the parse runs over an HcBlock.
+struct HcNoDict {
+    static constexpr bool kNone = true;
+    __device__ const HcNoDict& chunk() const { return *this; }
+    __device__ static constexpr bool ok() { return true; }
+    bool given() const { return true; }
+    HcNoDict from(uint32_t) const { return *this; }
 };
-__device__ __forceinline__ HcSetDict hc_set_dict(const uint32_t* __restrict__ chunkDict,
-                                                 const uint8_t* const* __restrict__ dictPtrs,
-                                                 const uint32_t* __restrict__ dictSizes, uint32_t nDicts,
-                                                 const uint8_t* __restrict__ states) {
-    const uint32_t k = chunkDict[blockIdx.x];
-    HcSetDict r{nullptr, nullptr, 0u, k == kBatchNoDict};
-    if (k < nDicts) {   // (kBatchNoDict is no index: nDicts <= 0xFFFFFFFF)
-        const uint32_t size = dictSizes[k];
-        const uint8_t* dp = dictPtrs[k];
-        r.E = size < kDictWindow ? size : kDictWindow;
-        r.dictEnd = dp + size;
-        r.state = states + (uint64_t)k * kHcDictStateBytes;
-        r.ok = (dp || size == 0) && hc_dict_state_ok(r.state, r.E);
+// Section 5c: one dictionary for every chunk.  has() is a compile-time true
+// (the host refuses a null state), and ok() loads the state's two words only
+// when called: the kernels ask after the chunk's own test.
+struct HcSharedDict {
+    static constexpr bool kNone = false;
+    uint32_t E;
+    const uint8_t* state;
+    const uint8_t* dictEnd;
+    __device__ const HcSharedDict& chunk() const { return *this; }
+    __device__ bool ok() const { return hc_dict_state_ok(state, E); }
+    __device__ static constexpr bool has() { return true; }
+    bool given() const { return state != nullptr; }
+    HcSharedDict from(uint32_t) const { return *this; }
+};
+// Section 5e: a set of dictionaries and an index per chunk.  ok: the chunk
+// has no dictionary (kBatchNoDict: state == nullptr, E = 0), or names
+// dictionary k < nDicts that has a pointer or no size and whose state k is an
+// HC state for its effective size.
+// kBatchNoDict is served as an HcDictBlock with E = 0 behind a chain built
+// from an empty table (kPrevPlain: the deltas of HcNoDict): no position lies
+// below E, so neither `dict` nor `ddl` is ever read, and the parse writes
+// lz4mtHipCompressBatchEx's bytes (section 5c's E < 4 rule, pinned by the
+// fixture's 0-byte dictionary).  It needs no state.
+struct HcDictSet {
+    static constexpr bool kNone = false;
+    const uint8_t* const* dictPtrs;
+    const uint32_t* dictSizes;
+    uint32_t nDicts;
+    const uint8_t* states;
+    const uint32_t* chunkDict;
+    struct Chunk {
+        const uint8_t* dictEnd;
+        const uint8_t* state;   // nullptr: no dictionary
+        uint32_t E;
+        bool good;
+        __device__ bool ok() const { return good; }
+        __device__ bool has() const { return state != nullptr; }
+    };
+    __device__ __forceinline__ Chunk chunk() const {
+        const uint32_t k = chunkDict[blockIdx.x];
+        Chunk r{nullptr, nullptr, 0u, k == kBatchNoDict};
+        if (k < nDicts) {   // (kBatchNoDict is no index: nDicts <= 0xFFFFFFFF)
+            const uint32_t size = dictSizes[k];
+            const uint8_t* dp = dictPtrs[k];
+            r.E = hc_dict_effective(size);
+            r.dictEnd = dp + size;
+            r.state = states + (uint64_t)k * kHcDictStateBytes;
+            r.good = (dp || size == 0) && hc_dict_state_ok(r.state, r.E);
+        }
+        return r;
     }
-    return r;
+    bool given() const { return chunkDict != nullptr; }
+    HcDictSet from(uint32_t o) const { return HcDictSet{dictPtrs, dictSizes, nDicts, states, chunkDict + o}; }
+};
+
+// The block a parse kernel runs over
+__device__ __forceinline__ HcBlock hc_batch_block(const BatchChunk& c, const uint8_t* slot, const HcNoDict&,
+                                                  uint32_t attempts, bool pattern) {
+    return HcBlock{c.s, c.n, (g_cu16*)slot, attempts, pattern};
+}
+template <class D>
+__device__ __forceinline__ HcDictBlock hc_batch_block(const BatchChunk& c, const uint8_t* slot, const D& d,
+                                                      uint32_t attempts, bool pattern) {
+    return HcDictBlock{c.s, c.n, (g_cu16*)slot, (g_cu8*)d.dictEnd - d.E, (g_cu16*)(d.state + kHcDictLinksAt), d.E,
+                       attempts, pattern};
 }
 
-// k_hc_prev_batch_dict with the heads read from the chunk's own state; without
-// a dictionary the chain of k_hc_prev_batch.  Refusal and choice are
-// workgroup-uniform (blockIdx.x only) and come before the first barrier.
-__global__ void __launch_bounds__(kPrevThreads) k_hc_prev_batch_dict_set(
-    const uint8_t* const* __restrict__ srcPtrs, const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
-    uint8_t* const* __restrict__ dstPtrs, uint8_t* __restrict__ ws, uint64_t slotBytes,
-    const uint8_t* const* __restrict__ dictPtrs, const uint32_t* __restrict__ dictSizes, uint32_t nDicts,
-    const uint8_t* __restrict__ states, const uint32_t* __restrict__ chunkDict) {
+// The chain of every chunk of the round, one workgroup per chunk; behind a
+// dictionary `last` starts from the state's heads.  The refusal (a size above
+// maxChunk would not fit the slot) and the choice are workgroup-uniform
+// (blockIdx.x only) and come before the first __syncthreads; hc_prev_range's
+// early end for n < 4 is uniform as well.
+template <class DICT>
+__global__ void __launch_bounds__(kPrevThreads) k_hc_prev_batch(const uint8_t* const* __restrict__ srcPtrs,
+                                                                const uint32_t* __restrict__ srcSizes,
+                                                                uint32_t maxChunk,
+                                                                uint8_t* const* __restrict__ dstPtrs,
+                                                                uint8_t* __restrict__ ws, uint64_t slotBytes,
+                                                                DICT dict) {
     __shared__ uint32_t last[1u << kHashLog];
     __shared__ uint8_t dd[4 * 1024];
     __shared__ __attribute__((aligned(16))) uint32_t ring[2048];
     const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, nullptr);
-    const HcSetDict D = hc_set_dict(chunkDict, dictPtrs, dictSizes, nDicts, states);
-    if (c.bad || !D.ok) return;
+    const auto& D = dict.chunk();
+    if (c.bad || !D.ok()) return;
     g_u16* dl = (g_u16*)(ws + (uint64_t)blockIdx.x * slotBytes);
-    if (D.state)
-        hc_prev_range<kPrevChunk>(c.s, c.n, dl, (l_u32*)last, (l_u8*)dd, (l_u32*)ring,
-                                  (const uint32_t*)(D.state + kHcDictHeadsAt), D.E);
-    else
-        hc_prev_range<kPrevPlain>(c.s, c.n, dl, (l_u32*)last, (l_u8*)dd, (l_u32*)ring);
+    if constexpr (!DICT::kNone) {
+        if (D.has()) {
+            hc_prev_range<kPrevChunk>(c.s, c.n, dl, (l_u32*)last, (l_u8*)dd, (l_u32*)ring,
+                                      (const uint32_t*)(D.state + kHcDictHeadsAt), D.E);
+            return;
+        }
+    }
+    hc_prev_range<kPrevPlain>(c.s, c.n, dl, (l_u32*)last, (l_u8*)dd, (l_u32*)ring);
 }
 
-__device__ __forceinline__ HcDictBlock hc_set_block(const BatchChunk& c, const uint8_t* slot, const HcSetDict& D,
-                                                    uint32_t attempts, bool pattern) {
-    return HcDictBlock{c.s, c.n, (g_cu16*)slot, (g_cu8*)D.dictEnd - D.E, (g_cu16*)(D.state + kHcDictLinksAt), D.E,
-                       attempts, pattern};
-}
-
-// Levels 3..9 / 10..12: k_encode_hc_batch_dict / k_encode_hc_opt_batch_dict with the dictionary of hc_set_dict
-__global__ void __launch_bounds__(64) k_encode_hc_batch_dict_set(
-    const uint8_t* const* __restrict__ srcPtrs, const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
-    uint8_t* const* __restrict__ dstPtrs, const uint32_t* __restrict__ dstCaps, int32_t* __restrict__ outSizes,
-    const uint8_t* __restrict__ ws, uint64_t slotBytes, uint32_t maxAttempts,
-    const uint8_t* const* __restrict__ dictPtrs, const uint32_t* __restrict__ dictSizes, uint32_t nDicts,
-    const uint8_t* __restrict__ states, const uint32_t* __restrict__ chunkDict) {
+// Levels 3..9: the hashChain parse of chunk blockIdx.x, one wave
+template <class DICT>
+__global__ void __launch_bounds__(64) k_encode_hc_batch(const uint8_t* const* __restrict__ srcPtrs,
+                                                        const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
+                                                        uint8_t* const* __restrict__ dstPtrs,
+                                                        const uint32_t* __restrict__ dstCaps,
+                                                        int32_t* __restrict__ outSizes,
+                                                        const uint8_t* __restrict__ ws, uint64_t slotBytes,
+                                                        uint32_t maxAttempts, DICT dict) {
     const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, dstCaps);
-    const HcSetDict D = hc_set_dict(chunkDict, dictPtrs, dictSizes, nDicts, states);
+    const auto& D = dict.chunk();
     int32_t r = kBatchBadChunk;
-    if (!c.bad && D.ok) {
-        const HcDictBlock B = hc_set_block(c, ws + (uint64_t)blockIdx.x * slotBytes, D, maxAttempts, maxAttempts > 128);
+    if (!c.bad && D.ok()) {
+        const auto B = hc_batch_block(c, ws + (uint64_t)blockIdx.x * slotBytes, D, maxAttempts, maxAttempts > 128);
         r = encode_block_hc(B, c.d, c.cap);
     }
     if (laneid() == 0) outSizes[blockIdx.x] = r;
 }
 
-__global__ void __launch_bounds__(64) k_encode_hc_opt_batch_dict_set(
-    const uint8_t* const* __restrict__ srcPtrs, const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
-    uint8_t* const* __restrict__ dstPtrs, const uint32_t* __restrict__ dstCaps, int32_t* __restrict__ outSizes,
-    uint8_t* ws, uint64_t slotBytes, uint64_t tableAt, uint32_t nbSearches, int32_t sufficientLen, int32_t fullUpdate,
-    const uint8_t* const* __restrict__ dictPtrs, const uint32_t* __restrict__ dictSizes, uint32_t nDicts,
-    const uint8_t* __restrict__ states, const uint32_t* __restrict__ chunkDict) {
+// Levels 10..12: the optimal parse of chunk blockIdx.x, one wave, the price
+// table after the slot's deltas (global memory, as k_encode_hc_opt_g's)
+template <class DICT>
+__global__ void __launch_bounds__(64) k_encode_hc_opt_batch(const uint8_t* const* __restrict__ srcPtrs,
+                                                            const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
+                                                            uint8_t* const* __restrict__ dstPtrs,
+                                                            const uint32_t* __restrict__ dstCaps,
+                                                            int32_t* __restrict__ outSizes, uint8_t* ws,
+                                                            uint64_t slotBytes, uint64_t tableAt, uint32_t nbSearches,
+                                                            int32_t sufficientLen, int32_t fullUpdate, DICT dict) {
     const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, dstCaps);
-    const HcSetDict D = hc_set_dict(chunkDict, dictPtrs, dictSizes, nDicts, states);
+    const auto& D = dict.chunk();
     int32_t r = kBatchBadChunk;
-    if (!c.bad && D.ok) {
+    if (!c.bad && D.ok()) {
         uint8_t* slot = ws + (uint64_t)blockIdx.x * slotBytes;
-        const HcDictBlock B = hc_set_block(c, slot, D, nbSearches, true);
+        const auto B = hc_batch_block(c, slot, D, nbSearches, true);   // pattern analysis always on
         r = encode_block_hc_opt(B, c.d, c.cap, hc_opt_at(slot + tableAt, 0), sufficientLen, fullUpdate != 0);
     }
     if (laneid() == 0) outSizes[blockIdx.x] = r;
 }
+
 
 // ---------------------------------------------------------------------------
 // Split parse of large blocks. A 4 MiB block is one serial hashChain parse
@@ -1806,30 +1740,35 @@ uint64_t hc_batch_slot_bytes(uint32_t maxChunk, int level) {
 // a round uses slot k.  Stream order keeps a round's parse after its chains
 // and the next round's chains after this round's parse.  Nothing but
 // launches: no allocation, no synchronisation, no environment.
-hipError_t launch_encode_hc_batch(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
-                                  uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps,
-                                  int32_t* outSizes, int level, uint8_t* ws, uint32_t slots, hipStream_t st) {
-    if (level < 3 || slots == 0 || !ws) return hipErrorInvalidValue;
-    slots = std::min(slots, kHcBatchSlots);
+template <class DICT>
+static hipError_t encode_hc_batch_rounds(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
+                                         uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps,
+                                         int32_t* outSizes, const DICT& dict, int level, uint8_t* ws, uint32_t slots,
+                                         hipStream_t st) {
+    if (level < 3 || slots == 0 || !ws || !dict.given()) return hipErrorInvalidValue;
     const uint32_t att = hc_attempts(level);
     const int lv = level > 12 ? 12 : level;
     const int32_t tl = lv == 10 ? 64 : lv == 11 ? 128 : kOptNum, fu = lv == 12 ? 1 : 0;   // as launch_encode_hc
     const uint64_t slotBytes = hc_batch_slot_bytes(maxChunk, level), tableAt = hc_batch_delta_bytes(maxChunk);
-    for (uint32_t o = 0; o < nChunks;) {
-        const uint32_t g = std::min(nChunks - o, slots);
+    return launch_slices(nChunks, std::min(slots, kHcBatchSlots), [&](uint32_t o, uint32_t g) {
         const uint32_t* caps = dstCaps ? dstCaps + o : nullptr;
-        hipLaunchKernelGGL(k_hc_prev_batch, dim3(g), dim3(kPrevThreads), 0, st, srcPtrs + o, srcSizes + o, maxChunk,
-                           dstPtrs + o, ws, slotBytes);
+        const DICT d = dict.from(o);
+        hipLaunchKernelGGL(k_hc_prev_batch<DICT>, dim3(g), dim3(kPrevThreads), 0, st, srcPtrs + o, srcSizes + o,
+                           maxChunk, dstPtrs + o, ws, slotBytes, d);
         if (lv >= 10)
-            hipLaunchKernelGGL(k_encode_hc_opt_batch, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, maxChunk,
-                               dstPtrs + o, caps, outSizes + o, ws, slotBytes, tableAt, att, tl, fu);
+            hipLaunchKernelGGL(k_encode_hc_opt_batch<DICT>, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o,
+                               maxChunk, dstPtrs + o, caps, outSizes + o, ws, slotBytes, tableAt, att, tl, fu, d);
         else
-            hipLaunchKernelGGL(k_encode_hc_batch, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, maxChunk,
-                               dstPtrs + o, caps, outSizes + o, (const uint8_t*)ws, slotBytes, att);
-        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        o += g;
-    }
-    return hipSuccess;
+            hipLaunchKernelGGL(k_encode_hc_batch<DICT>, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, maxChunk,
+                               dstPtrs + o, caps, outSizes + o, (const uint8_t*)ws, slotBytes, att, d);
+    });
+}
+
+hipError_t launch_encode_hc_batch(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
+                                  uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps,
+                                  int32_t* outSizes, int level, uint8_t* ws, uint32_t slots, hipStream_t st) {
+    return encode_hc_batch_rounds(srcPtrs, srcSizes, maxChunk, nChunks, dstPtrs, dstCaps, outSizes, HcNoDict{}, level,
+                                  ws, slots, st);
 }
 
 // The dictionary operators (section 5c).  dictEnd / E: one past the
@@ -1840,82 +1779,35 @@ hipError_t launch_hc_dict_prepare(const uint8_t* dictEnd, uint32_t E, uint8_t* s
     return hipGetLastError();
 }
 
-// launch_encode_hc_batch's rounds and slots, every chunk behind the dictionary
 hipError_t launch_encode_hc_batch_dict(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
                                        uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps,
                                        int32_t* outSizes, const uint8_t* dictEnd, uint32_t E, const uint8_t* state,
                                        int level, uint8_t* ws, uint32_t slots, hipStream_t st) {
-    if (level < 3 || slots == 0 || !ws || !state) return hipErrorInvalidValue;
-    slots = std::min(slots, kHcBatchSlots);
-    const uint32_t att = hc_attempts(level);
-    const int lv = level > 12 ? 12 : level;
-    const int32_t tl = lv == 10 ? 64 : lv == 11 ? 128 : kOptNum, fu = lv == 12 ? 1 : 0;   // as launch_encode_hc
-    const uint64_t slotBytes = hc_batch_slot_bytes(maxChunk, level), tableAt = hc_batch_delta_bytes(maxChunk);
-    for (uint32_t o = 0; o < nChunks;) {
-        const uint32_t g = std::min(nChunks - o, slots);
-        const uint32_t* caps = dstCaps ? dstCaps + o : nullptr;
-        hipLaunchKernelGGL(k_hc_prev_batch_dict, dim3(g), dim3(kPrevThreads), 0, st, srcPtrs + o, srcSizes + o,
-                           maxChunk, dstPtrs + o, ws, slotBytes, state, E);
-        if (lv >= 10)
-            hipLaunchKernelGGL(k_encode_hc_opt_batch_dict, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o,
-                               maxChunk, dstPtrs + o, caps, outSizes + o, ws, slotBytes, tableAt, att, tl, fu, dictEnd,
-                               E, state);
-        else
-            hipLaunchKernelGGL(k_encode_hc_batch_dict, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, maxChunk,
-                               dstPtrs + o, caps, outSizes + o, (const uint8_t*)ws, slotBytes, att, dictEnd, E, state);
-        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        o += g;
-    }
-    return hipSuccess;
+    return encode_hc_batch_rounds(srcPtrs, srcSizes, maxChunk, nChunks, dstPtrs, dstCaps, outSizes,
+                                  HcSharedDict{E, state, dictEnd}, level, ws, slots, st);
 }
 
 // The same with a set of dictionaries (section 5e): every array is device
 // memory; state k at states + k * kHcDictStateBytes, 256-byte aligned.  One
-// workgroup per dictionary, a launch per kHcSetGrid dictionaries.
-constexpr uint32_t kHcSetGrid = 1u << 30;
+// workgroup per dictionary.
 hipError_t launch_hc_dict_set_prepare(const uint8_t* const* dictPtrs, const uint32_t* dictSizes, uint32_t nDicts,
                                       uint8_t* states, hipStream_t st) {
-    for (uint32_t o = 0; o < nDicts;) {
-        const uint32_t g = std::min(nDicts - o, kHcSetGrid);
+    return launch_slices(nDicts, kBatchGrid, [&](uint32_t o, uint32_t g) {
         hipLaunchKernelGGL(k_hc_dict_set_prepare, dim3(g), dim3(kPrevThreads), 0, st, dictPtrs + o, dictSizes + o,
                            states + (uint64_t)o * kHcDictStateBytes);
-        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        o += g;
-    }
-    return hipSuccess;
+    });
 }
 
-// launch_encode_hc_batch_dict's rounds and slots; a round slices chunkDict with
-// the other chunk arrays, the dictionary arrays and the states are the call's
+// A round slices chunkDict with the other chunk arrays; the dictionary arrays
+// and the states are the call's
 hipError_t launch_encode_hc_batch_dict_set(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
                                            uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps,
                                            int32_t* outSizes, const uint8_t* const* dictPtrs,
                                            const uint32_t* dictSizes, uint32_t nDicts, const uint8_t* states,
                                            const uint32_t* chunkDict, int level, uint8_t* ws, uint32_t slots,
                                            hipStream_t st) {
-    if (level < 3 || slots == 0 || !ws || !chunkDict) return hipErrorInvalidValue;
-    slots = std::min(slots, kHcBatchSlots);
-    const uint32_t att = hc_attempts(level);
-    const int lv = level > 12 ? 12 : level;
-    const int32_t tl = lv == 10 ? 64 : lv == 11 ? 128 : kOptNum, fu = lv == 12 ? 1 : 0;   // as launch_encode_hc
-    const uint64_t slotBytes = hc_batch_slot_bytes(maxChunk, level), tableAt = hc_batch_delta_bytes(maxChunk);
-    for (uint32_t o = 0; o < nChunks;) {
-        const uint32_t g = std::min(nChunks - o, slots);
-        const uint32_t* caps = dstCaps ? dstCaps + o : nullptr;
-        hipLaunchKernelGGL(k_hc_prev_batch_dict_set, dim3(g), dim3(kPrevThreads), 0, st, srcPtrs + o, srcSizes + o,
-                           maxChunk, dstPtrs + o, ws, slotBytes, dictPtrs, dictSizes, nDicts, states, chunkDict + o);
-        if (lv >= 10)
-            hipLaunchKernelGGL(k_encode_hc_opt_batch_dict_set, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o,
-                               maxChunk, dstPtrs + o, caps, outSizes + o, ws, slotBytes, tableAt, att, tl, fu, dictPtrs,
-                               dictSizes, nDicts, states, chunkDict + o);
-        else
-            hipLaunchKernelGGL(k_encode_hc_batch_dict_set, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o,
-                               maxChunk, dstPtrs + o, caps, outSizes + o, (const uint8_t*)ws, slotBytes, att, dictPtrs,
-                               dictSizes, nDicts, states, chunkDict + o);
-        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        o += g;
-    }
-    return hipSuccess;
+    return encode_hc_batch_rounds(srcPtrs, srcSizes, maxChunk, nChunks, dstPtrs, dstCaps, outSizes,
+                                  HcDictSet{dictPtrs, dictSizes, nDicts, states, chunkDict}, level, ws, slots, st);
 }
 
 }  // namespace lz4mt

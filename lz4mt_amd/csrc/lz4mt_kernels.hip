@@ -1633,11 +1633,12 @@ static_assert(kDictStateBytes % 16 == 0 && kDictStateBytes / 4 > 4096 && kDictWi
 // Buckets nothing was inserted into stay 0.  One workgroup: at most 21 846
 // positions, the table in LDS.  dictEnd: one past the dictionary's last byte;
 // it is read by bytes (any alignment, nothing outside [dictEnd - D, dictEnd)).
-__global__ void __launch_bounds__(1024) k_dict_prepare(const uint8_t* __restrict__ dictEnd, uint32_t D,
-                                                       uint32_t* __restrict__ state) {
+// Every word of the state is written; `recorded` is what word 4096 keeps: D,
+// or kDictStateBad (lz4mt_device.h).
+__device__ __forceinline__ void dict_prepare(const uint8_t* dictEnd, uint32_t D, uint32_t recorded, uint32_t* state,
+                                             uint32_t* Tp) {
     using G = V5Geo<false, false, true>;
     static_assert(G::PB + G::TB == 32 && G::TB == 9, "the packed (position, tag) fits a word");
-    __shared__ uint32_t Tp[4096];
     const uint32_t t = threadIdx.x;
     for (uint32_t i = t; i < 4096; i += 1024) Tp[i] = 0;
     __syncthreads();
@@ -1660,150 +1661,118 @@ __global__ void __launch_bounds__(1024) k_dict_prepare(const uint8_t* __restrict
             const uint32_t e = Tp[i];
             v = (e >> G::TB) | (e << G::PB);
         } else if (i == 4096) {
-            v = D;
+            v = recorded;
         }
         state[i] = v;
     }
 }
 
+__global__ void __launch_bounds__(1024) k_dict_prepare(const uint8_t* __restrict__ dictEnd, uint32_t D,
+                                                       uint32_t* __restrict__ state) {
+    __shared__ uint32_t Tp[4096];
+    dict_prepare(dictEnd, D, D, state, Tp);
+}
+
+// Workgroup k for dictionary k of a set (lz4mt_hip.h section 5d; pointer and
+// size are uniform scalar loads): what the host does for the shared
+// dictionary happens here, the effective size and the dictionary's end, ptr +
+// size in 64-bit arithmetic.  State k is kDictStateBytes further than state
+// k - 1.  An effective dictionary without a pointer is built as none and
+// recorded as kDictStateBad.
+__global__ void __launch_bounds__(1024) k_dict_set_prepare(const uint8_t* const* __restrict__ dictPtrs,
+                                                           const uint32_t* __restrict__ dictSizes,
+                                                           uint32_t* __restrict__ states) {
+    __shared__ uint32_t Tp[4096];
+    const uint32_t k = blockIdx.x, size = dictSizes[k];
+    const uint8_t* dp = dictPtrs[k];
+    const uint32_t D = dict_effective(size);
+    const bool bad = !dp && D != 0;
+    dict_prepare(dp + size, bad ? 0u : D, bad ? kDictStateBad : D, states + (uint64_t)k * (kDictStateBytes / 4), Tp);
+}
+
+// The chunk's dictionary source, as lz4mt_hc.hip's (its comment states what a
+// source answers): one dictionary for every chunk, or a set and an index per
+// chunk.  kDup: the encoder instantiation (DUP) of the source's kernel, so
+// that each stays the single call site it is inlined at.
+// SharedDict (section 5b): a state built for another dictionary size refuses
+// every chunk; has() is a compile-time true (the host refuses a null state).
+struct SharedDict {
+    static constexpr bool kDup = false;
+    const uint8_t* dictEnd;
+    uint32_t D;
+    const uint32_t* state;
+    __device__ const SharedDict& chunk() const { return *this; }
+    __device__ bool ok() const { return state[4096] == D; }
+    __device__ static constexpr bool has() { return true; }
+};
+// DictSet (section 5d).  Refused, with nothing written: an index that names
+// no dictionary, a dictionary with a size and no pointer, a state recorded for
+// another effective size.  kBatchNoDict needs no state: a fresh stream.
+struct DictSet {
+    static constexpr bool kDup = true;
+    const uint8_t* const* dictPtrs;
+    const uint32_t* dictSizes;
+    uint32_t nDicts;
+    const uint32_t* states;
+    const uint32_t* chunkDict;
+    struct Chunk {
+        const uint8_t* dictEnd;
+        const uint32_t* state;   // nullptr: no dictionary
+        uint32_t D;
+        bool good;
+        __device__ bool ok() const { return good; }
+        __device__ bool has() const { return state != nullptr; }
+    };
+    __device__ __forceinline__ Chunk chunk() const {
+        const uint32_t k = chunkDict[blockIdx.x];
+        Chunk r{nullptr, nullptr, 0u, k == kBatchNoDict};
+        if (k < nDicts) {   // (kBatchNoDict is no index: nDicts <= 0xFFFFFFFF)
+            const uint32_t size = dictSizes[k];
+            const uint8_t* dp = dictPtrs[k];
+            r.D = dict_effective(size);
+            r.dictEnd = dp + size;
+            r.state = states + (uint64_t)k * (kDictStateBytes / 4);
+            r.good = (dp || size == 0) && r.state[4096] == r.D;
+        }
+        return r;
+    }
+};
+
 // One wave per chunk, k_encode_batch's conventions (no wait on another wave,
-// no loop over chunks, no atomics).  The 16 KiB table comes from the state
-// into LDS (read-only, shared by every wave: it stays in L2); the LINK / XH /
-// XD encoder then runs one stream step: catch-up bound kLinkO0 for a
-// candidate in the chunk, kLinkO0 - D for one in the dictionary, candidates
-// below kLinkO0 - D refused (dictSmall; with D = 64 KiB the bound is 0 and
-// the distance test alone decides, noDictIssue).  k_encode's LDS layout, 20
-// KiB and 8 waves per CU.  A state built for another dictionary size refuses
-// every chunk.
-template <bool XC>
+// no loop over chunks, no atomics).  The 16 KiB table comes from the chunk's
+// state into LDS (read-only, shared by every wave: it stays in L2), or is
+// zeroed for a chunk without a dictionary; the LINK / XH / XD encoder then
+// runs one stream step: catch-up bound kLinkO0 for a candidate in the chunk,
+// kLinkO0 - D for one in the dictionary, candidates below kLinkO0 - D refused
+// (dictSmall; with D = 64 KiB the bound is 0 and the distance test alone
+// decides, noDictIssue).  k_encode's LDS layout, 20 KiB and 8 waves per CU.
+template <bool XC, class DICT>
 __global__ void __launch_bounds__(64) k_encode_batch_dict(const uint8_t* const* __restrict__ srcPtrs,
                                                           const uint32_t* __restrict__ srcSizes, uint32_t maxChunk,
                                                           uint8_t* const* __restrict__ dstPtrs,
                                                           const uint32_t* __restrict__ dstCaps,
-                                                          int32_t* __restrict__ outSizes,
-                                                          const uint8_t* __restrict__ dictEnd, uint32_t D,
-                                                          const uint32_t* __restrict__ state) {
+                                                          int32_t* __restrict__ outSizes, DICT dict) {
     ENCODE_LDS
     (void)S;
     const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, dstCaps);
     const uint32_t L = laneid();
     int32_t r = kBatchBadChunk;
-    if (!c.bad && state[4096] == D) {
-        g_cu4* in = (g_cu4*)state;
-        for (uint32_t i = L; i < 1024; i += 64) ((l_u4*)T)[i] = in[i];
-        WAVE_SYNC();
-        const LinkArgs lk{kLinkO0, kLinkO0 - D, kLinkO0 - D, false};
-        r = encode_block_v5<false, false, false, true, false, false, true, XC, false, true>(
-            c.s - kLinkO0, kLinkO0 + c.n, c.d, c.cap, (l_u32*)T, (l_u8*)X, nullptr, lk, nullptr,
-            gptr(dictEnd) - kLinkO0);
-    }
-    if (L == 0) outSizes[blockIdx.x] = r;
-}
-
-// ---- the same with a set of dictionaries and an index per chunk
-// (lz4mt_hip.h section 5d).  The dictionaries' pointers and sizes are device
-// arrays, so what the host did for the shared dictionary happens here: the
-// effective size (dict_effective) and the dictionary's end, ptr + size in
-// 64-bit arithmetic.  State k is kDictStateBytes further than state k - 1
-// and byte for byte what k_dict_prepare writes for dictionary k.
-// kDictStateBad: the recorded size (word 4096) of a dictionary that has a
-// size and no pointer.  No effective size equals it, so the encoder's guard
-// refuses the chunks that name such a state.
-constexpr uint32_t kDictStateBad = 0xFFFFFFFFu;
-static_assert(kDictStateBad > kDictWindow, "no effective size");
-__device__ __forceinline__ uint32_t dict_effective_dev(uint32_t dictSize) {
-    return dictSize < kDictHashUnit ? 0u : (dictSize < kDictWindow ? dictSize : kDictWindow);
-}
-
-// k_dict_prepare's work, workgroup k for dictionary k (pointer and size are
-// uniform scalar loads).
-__global__ void __launch_bounds__(1024) k_dict_set_prepare(const uint8_t* const* __restrict__ dictPtrs,
-                                                           const uint32_t* __restrict__ dictSizes,
-                                                           uint32_t* __restrict__ states) {
-    using G = V5Geo<false, false, true>;
-    __shared__ uint32_t Tp[4096];
-    const uint32_t t = threadIdx.x, k = blockIdx.x;
-    const uint32_t size = dictSizes[k];
-    const uint8_t* dp = dictPtrs[k];
-    const uint32_t D = dict_effective_dev(size);
-    const bool bad = !dp && D != 0;
-    g_u32* state = (g_u32*)states + (uint64_t)k * (kDictStateBytes / 4);
-    for (uint32_t i = t; i < 4096; i += 1024) Tp[i] = 0;
-    __syncthreads();
-    if (D >= kDictHashUnit && !bad) {
-        g_cu8* h = gptr(dp) + size - kLinkO0;   // h[p]: the byte at position p, valid for p in [kLinkO0 - D, kLinkO0)
-        const uint32_t lo = kLinkO0 - D;
-        const uint32_t cnt = (D - kDictHashUnit) / 3 + 1;
-        for (uint32_t j = t; j < cnt; j += 1024) {
-            const uint32_t p = lo + 3 * j;
-            uint32_t w0 = 0, b4 = h[p + 4];
-            for (uint32_t q = 0; q < 4; ++q) w0 |= (uint32_t)h[p + q] << (8 * q);
-            const uint32_t hs = lz4_hash<false>(w0, b4);
-            atomicMax(&Tp[hs], (p << G::TB) | G::tag(w0));
-        }
-    }
-    __syncthreads();
-    for (uint32_t i = t; i < kDictStateBytes / 4; i += 1024) {
-        uint32_t v = 0;
-        if (i < 4096) {
-            const uint32_t e = Tp[i];
-            v = (e >> G::TB) | (e << G::PB);
-        } else if (i == 4096) {
-            v = bad ? kDictStateBad : D;
-        }
-        state[i] = v;
-    }
-}
-
-// k_encode_batch_dict with the dictionary chosen per chunk: the wave reads
-// its index, then that dictionary's pointer and size and word 4096 of its
-// state (all uniform), copies that state's table into LDS -- or zeroes the
-// table for kBatchNoDict, which needs no state: a fresh stream -- and runs the
-// same stream step.  Refused, with nothing written: an index that names no
-// dictionary, a dictionary with a size and no pointer, a state recorded for
-// another effective size.  The encoder is an instantiation of its own (DUP),
-// so that k_encode_batch_dict's stays the single call site it is inlined at.
-template <bool XC>
-__global__ void __launch_bounds__(64) k_encode_batch_dict_set(const uint8_t* const* __restrict__ srcPtrs,
-                                                              const uint32_t* __restrict__ srcSizes,
-                                                              uint32_t maxChunk, uint8_t* const* __restrict__ dstPtrs,
-                                                              const uint32_t* __restrict__ dstCaps,
-                                                              int32_t* __restrict__ outSizes,
-                                                              const uint8_t* const* __restrict__ dictPtrs,
-                                                              const uint32_t* __restrict__ dictSizes, uint32_t nDicts,
-                                                              const uint32_t* __restrict__ states,
-                                                              const uint32_t* __restrict__ chunkDict) {
-    ENCODE_LDS
-    (void)S;
-    const BatchChunk c = batch_chunk(srcPtrs, srcSizes, maxChunk, dstPtrs, dstCaps);
-    const uint32_t L = laneid();
-    const uint32_t k = chunkDict[blockIdx.x];
-    int32_t r = kBatchBadChunk;
-    bool ok = !c.bad;
-    uint32_t D = 0;
-    g_cu8* dictEnd = nullptr;
-    if (ok && k != kBatchNoDict) {
-        ok = k < nDicts;
-        if (ok) {
-            const uint32_t size = dictSizes[k];
-            const uint8_t* dp = dictPtrs[k];
-            g_cu32* state = (g_cu32*)states + (uint64_t)k * (kDictStateBytes / 4);
-            D = dict_effective_dev(size);
-            dictEnd = gptr(dp) + size;
-            ok = (dp || size == 0) && state[4096] == D;
-            if (ok) {
-                g_cu4* in = (g_cu4*)state;
+    if (!c.bad) {
+        const auto& d = dict.chunk();
+        if (d.ok()) {
+            if (d.has()) {
+                g_cu4* in = (g_cu4*)d.state;
                 for (uint32_t i = L; i < 1024; i += 64) ((l_u4*)T)[i] = in[i];
+            } else {
+                for (uint32_t i = L; i < 1024; i += 64) ((l_u4*)T)[i] = (v4u){0, 0, 0, 0};
             }
+            WAVE_SYNC();
+            const LinkArgs lk{kLinkO0, kLinkO0 - d.D, kLinkO0 - d.D, false};
+            [[clang::always_inline]] r =
+                encode_block_v5<false, false, false, true, false, false, true, XC, DICT::kDup, true>(
+                    c.s - kLinkO0, kLinkO0 + c.n, c.d, c.cap, (l_u32*)T, (l_u8*)X, nullptr, lk, nullptr,
+                    gptr(d.dictEnd) - kLinkO0);
         }
-    } else if (ok) {
-        for (uint32_t i = L; i < 1024; i += 64) ((l_u4*)T)[i] = (v4u){0, 0, 0, 0};
-    }
-    if (ok) {
-        WAVE_SYNC();
-        const LinkArgs lk{kLinkO0, kLinkO0 - D, kLinkO0 - D, false};
-        [[clang::always_inline]] r = encode_block_v5<false, false, false, true, false, false, true, XC, true, true>(
-            c.s - kLinkO0, kLinkO0 + c.n, c.d, c.cap, (l_u32*)T, (l_u8*)X, nullptr, lk, nullptr, dictEnd - kLinkO0);
     }
     if (L == 0) outSizes[blockIdx.x] = r;
 }
@@ -2267,7 +2236,6 @@ hipError_t launch_encode(const uint8_t* src, uint64_t srcSize, uint32_t blockSiz
 // All arrays are device memory; dstCaps may be null (every capacity the
 // bound).  maxChunk <= kBatchMaxChunk (the caller checked).  A grid holds at
 // most kBatchGrid chunks; longer batches go out in slices of the arrays.
-constexpr uint32_t kBatchGrid = 1u << 30;
 hipError_t launch_encode_batch(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
                                uint32_t nChunks, uint8_t* const* dstPtrs, const uint32_t* dstCaps, int32_t* outSizes,
                                hipStream_t st) {
@@ -2276,14 +2244,10 @@ hipError_t launch_encode_batch(const uint8_t* const* srcPtrs, const uint32_t* sr
     const bool small = maxChunk < (uint32_t)kLimit64K;
     const auto k = small ? (xc ? k_encode_batch16<true> : k_encode_batch16<false>)
                          : (xc ? k_encode_batch<true> : k_encode_batch<false>);
-    for (uint32_t o = 0; o < nChunks;) {
-        const uint32_t g = std::min(nChunks - o, kBatchGrid);
+    return launch_slices(nChunks, kBatchGrid, [&](uint32_t o, uint32_t g) {
         hipLaunchKernelGGL(k, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, maxChunk, dstPtrs + o,
                            dstCaps ? dstCaps + o : nullptr, outSizes + o);
-        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        o += g;
-    }
-    return hipSuccess;
+    });
 }
 
 // The dictionary operators.  dictEnd / D: the effective dictionary
@@ -2299,29 +2263,21 @@ hipError_t launch_encode_batch_dict(const uint8_t* const* srcPtrs, const uint32_
                                     hipStream_t st) {
     bool xc = true;
     if (const hipError_t r = encoder_path(st, &xc); r != hipSuccess) return r;
-    const auto k = xc ? k_encode_batch_dict<true> : k_encode_batch_dict<false>;
-    for (uint32_t o = 0; o < nChunks;) {
-        const uint32_t g = std::min(nChunks - o, kBatchGrid);
+    const auto k = xc ? k_encode_batch_dict<true, SharedDict> : k_encode_batch_dict<false, SharedDict>;
+    return launch_slices(nChunks, kBatchGrid, [&](uint32_t o, uint32_t g) {
         hipLaunchKernelGGL(k, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, maxChunk, dstPtrs + o,
-                           dstCaps ? dstCaps + o : nullptr, outSizes + o, dictEnd, D, state);
-        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        o += g;
-    }
-    return hipSuccess;
+                           dstCaps ? dstCaps + o : nullptr, outSizes + o, SharedDict{dictEnd, D, state});
+    });
 }
 
 // The same with a set of dictionaries (section 5d): every array is device
 // memory; state k at states + k * kDictStateBytes, 256-byte aligned.
 hipError_t launch_dict_set_prepare(const uint8_t* const* dictPtrs, const uint32_t* dictSizes, uint32_t nDicts,
                                    uint32_t* states, hipStream_t st) {
-    for (uint32_t o = 0; o < nDicts;) {
-        const uint32_t g = std::min(nDicts - o, kBatchGrid);
+    return launch_slices(nDicts, kBatchGrid, [&](uint32_t o, uint32_t g) {
         hipLaunchKernelGGL(k_dict_set_prepare, dim3(g), dim3(1024), 0, st, dictPtrs + o, dictSizes + o,
                            states + (uint64_t)o * (kDictStateBytes / 4));
-        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        o += g;
-    }
-    return hipSuccess;
+    });
 }
 
 hipError_t launch_encode_batch_dict_set(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t maxChunk,
@@ -2331,16 +2287,12 @@ hipError_t launch_encode_batch_dict_set(const uint8_t* const* srcPtrs, const uin
                                         hipStream_t st) {
     bool xc = true;
     if (const hipError_t r = encoder_path(st, &xc); r != hipSuccess) return r;
-    const auto k = xc ? k_encode_batch_dict_set<true> : k_encode_batch_dict_set<false>;
-    for (uint32_t o = 0; o < nChunks;) {
-        const uint32_t g = std::min(nChunks - o, kBatchGrid);
+    const auto k = xc ? k_encode_batch_dict<true, DictSet> : k_encode_batch_dict<false, DictSet>;
+    return launch_slices(nChunks, kBatchGrid, [&](uint32_t o, uint32_t g) {
         hipLaunchKernelGGL(k, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, maxChunk, dstPtrs + o,
-                           dstCaps ? dstCaps + o : nullptr, outSizes + o, dictPtrs, dictSizes, nDicts, states,
-                           chunkDict + o);
-        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        o += g;
-    }
-    return hipSuccess;
+                           dstCaps ? dstCaps + o : nullptr, outSizes + o,
+                           DictSet{dictPtrs, dictSizes, nDicts, states, chunkDict + o});
+    });
 }
 #endif
 
@@ -3138,10 +3090,39 @@ __global__ void __launch_bounds__(64) k_decode(const uint8_t* __restrict__ frame
 
 // Batched block operator (lz4mt_hip.h section 5): wave blockIdx.x decodes
 // chunk blockIdx.x, always an LZ4 block (no frame bit, so never raw), into a
-// destination of exactly dstCaps[i] bytes: the slot that exists is the
+// destination of exactly cap = dstCaps[i] bytes: the slot that exists is the
 // capacity (physcap = cap), so every store is bounded by it.  The input
 // window loads no dword outside the chunk (Dec's HG).  k_decode's LDS, 8
 // waves per CU; as k_encode_batch, nothing here waits on another wave.
+// decode_batch_chunk: the decode of a chunk a kernel has not refused.  XD:
+// against a dictionary that ends at hist (any alignment), lowP the negative
+// of its reachable size.  Each kernel below is an instantiation of its own
+// (DUP), so that each stays the single call site it is inlined at.  The
+// refusal chain stays in the kernels: written inside this function it costs
+// k_decode_batch_dict two more SGPR spills and 20 instructions
+// (profiles/batch_dict_fold_object_diff.txt).
+template <bool XD, bool DUP>
+__device__ __forceinline__ int32_t decode_batch_chunk(const uint8_t* sp, uint32_t len, uint8_t* dp, uint32_t cap,
+                                                      g_cu8* hist, int32_t lowP, l_u8* ring, l_u8* win) {
+    Dec<false, true, XD, DUP> D;
+    if constexpr (XD) D.hist = hist;
+    D.acc = nullptr;
+    D.ts = 0;
+    D.src = gptr(sp);
+    D.len = (int64_t)len;
+    D.dst = gptr(dp);
+    D.physcap = (int64_t)cap;
+    D.ring = ring;
+    D.win = win;
+    D.wlo = INT64_MIN / 4;
+    D.labase = INT64_MIN / 4;
+    D.la = 0;
+    D.flushed = 0;
+    D.completed = 0;
+    D.lowP = lowP;
+    return decode_block(D, (int64_t)cap);
+}
+
 __global__ void __launch_bounds__(64) k_decode_batch(const uint8_t* const* __restrict__ srcPtrs,
                                                      const uint32_t* __restrict__ srcSizes,
                                                      uint8_t* const* __restrict__ dstPtrs,
@@ -3159,32 +3140,17 @@ __global__ void __launch_bounds__(64) k_decode_batch(const uint8_t* const* __res
     } else if (len > 0x7FFFFFFFu || cap > 0x7FFFFFFFu) {
         res = -1;   // lz4mtHipDecompressBlock's answer to a size or capacity that is no int
     } else {
-        Dec<false, true> D;
-        D.acc = nullptr;
-        D.ts = 0;
-        D.src = gptr(sp);
-        D.len = (int64_t)len;
-        D.dst = gptr(dp);
-        D.physcap = (int64_t)cap;
-        D.ring = (l_u8*)ring;
-        D.win = (l_u8*)win;
-        D.wlo = INT64_MIN / 4;
-        D.labase = INT64_MIN / 4;
-        D.la = 0;
-        D.flushed = 0;
-        D.completed = 0;
-        D.lowP = 0;
-        res = decode_block(D, (int64_t)cap);
+        res = decode_batch_chunk<false, false>(sp, len, dp, cap, nullptr, 0, (l_u8*)ring, (l_u8*)win);
         if (res == kDecodeOutputTooSmall) res = -1;   // (unreachable with physcap = cap; mapped as the block operator maps it)
     }
     if (laneid() == 0) outSizes[i] = res;
 }
 
 // The same against a shared dictionary of dictSize > 0 bytes that ends at
-// dictEnd (any alignment; only [dictEnd - dictSize, dictEnd) is read):
+// dictEnd (only [dictEnd - dictSize, dictEnd) is read):
 // LZ4_decompress_safe_usingDict with the dictionary away from dst.  An
 // offset is refused only below dst - dictSize, and only when dictSize < 64
-// KiB (an offset reaches 65535 at most).  k_decode_batch's LDS, 8 waves per CU.
+// KiB (an offset reaches 65535 at most).
 __global__ void __launch_bounds__(64) k_decode_batch_dict(const uint8_t* const* __restrict__ srcPtrs,
                                                           const uint32_t* __restrict__ srcSizes,
                                                           uint8_t* const* __restrict__ dstPtrs,
@@ -3203,23 +3169,8 @@ __global__ void __launch_bounds__(64) k_decode_batch_dict(const uint8_t* const* 
     } else if (len > 0x7FFFFFFFu || cap > 0x7FFFFFFFu) {
         res = -1;
     } else {
-        Dec<false, true, true> D;
-        D.hist = gptr(dictEnd);
-        D.acc = nullptr;
-        D.ts = 0;
-        D.src = gptr(sp);
-        D.len = (int64_t)len;
-        D.dst = gptr(dp);
-        D.physcap = (int64_t)cap;
-        D.ring = (l_u8*)ring;
-        D.win = (l_u8*)win;
-        D.wlo = INT64_MIN / 4;
-        D.labase = INT64_MIN / 4;
-        D.la = 0;
-        D.flushed = 0;
-        D.completed = 0;
-        D.lowP = -(int32_t)min(dictSize, 65536u);
-        res = decode_block(D, (int64_t)cap);
+        res = decode_batch_chunk<true, false>(sp, len, dp, cap, gptr(dictEnd), -(int32_t)min(dictSize, 65536u),
+                                              (l_u8*)ring, (l_u8*)win);
         if (res == kDecodeOutputTooSmall) res = -1;
     }
     if (laneid() == 0) outSizes[i] = res;
@@ -3234,8 +3185,7 @@ __global__ void __launch_bounds__(64) k_decode_batch_dict(const uint8_t* const* 
 // offset below the block is refused before a copy, and so out8 never sees a
 // position below 0: hist is not read.  Refused besides k_decode_batch's
 // chunks: an index that names no dictionary, a dictionary with a size and no
-// pointer.  An instantiation of its own (DUP), so that k_decode_batch_dict's
-// stays the single call site it is inlined at.
+// pointer.
 __global__ void __launch_bounds__(64) k_decode_batch_dict_set(const uint8_t* const* __restrict__ srcPtrs,
                                                               const uint32_t* __restrict__ srcSizes,
                                                               uint8_t* const* __restrict__ dstPtrs,
@@ -3267,23 +3217,8 @@ __global__ void __launch_bounds__(64) k_decode_batch_dict_set(const uint8_t* con
     } else if (len > 0x7FFFFFFFu || cap > 0x7FFFFFFFu) {
         res = -1;
     } else {
-        Dec<false, true, true, true> D;
-        D.hist = gptr(dict) + dictSize;
-        D.acc = nullptr;
-        D.ts = 0;
-        D.src = gptr(sp);
-        D.len = (int64_t)len;
-        D.dst = gptr(dp);
-        D.physcap = (int64_t)cap;
-        D.ring = (l_u8*)ring;
-        D.win = (l_u8*)win;
-        D.wlo = INT64_MIN / 4;
-        D.labase = INT64_MIN / 4;
-        D.la = 0;
-        D.flushed = 0;
-        D.completed = 0;
-        D.lowP = -(int32_t)min(dictSize, 65536u);
-        res = decode_block(D, (int64_t)cap);
+        res = decode_batch_chunk<true, true>(sp, len, dp, cap, gptr(dict) + dictSize,
+                                             -(int32_t)min(dictSize, 65536u), (l_u8*)ring, (l_u8*)win);
         if (res == kDecodeOutputTooSmall) res = -1;
     }
     if (laneid() == 0) outSizes[i] = res;
@@ -3875,44 +3810,29 @@ hipError_t launch_decode(const uint8_t* frame, const BlockRec* recs, uint32_t nB
 
 hipError_t launch_decode_batch(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t nChunks,
                                uint8_t* const* dstPtrs, const uint32_t* dstCaps, int32_t* outSizes, hipStream_t st) {
-    constexpr uint32_t kGrid = 1u << 30;   // chunks per grid; longer batches go out in slices of the arrays
-    for (uint32_t o = 0; o < nChunks;) {
-        const uint32_t g = std::min(nChunks - o, kGrid);
+    return launch_slices(nChunks, kBatchGrid, [&](uint32_t o, uint32_t g) {
         hipLaunchKernelGGL(k_decode_batch, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, dstPtrs + o,
                            dstCaps + o, outSizes + o);
-        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        o += g;
-    }
-    return hipSuccess;
+    });
 }
 
 hipError_t launch_decode_batch_dict(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t nChunks,
                                     uint8_t* const* dstPtrs, const uint32_t* dstCaps, int32_t* outSizes,
                                     const uint8_t* dictEnd, uint32_t dictSize, hipStream_t st) {
-    constexpr uint32_t kGrid = 1u << 30;
-    for (uint32_t o = 0; o < nChunks;) {
-        const uint32_t g = std::min(nChunks - o, kGrid);
+    return launch_slices(nChunks, kBatchGrid, [&](uint32_t o, uint32_t g) {
         hipLaunchKernelGGL(k_decode_batch_dict, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, dstPtrs + o,
                            dstCaps + o, outSizes + o, dictEnd, dictSize);
-        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        o += g;
-    }
-    return hipSuccess;
+    });
 }
 
 hipError_t launch_decode_batch_dict_set(const uint8_t* const* srcPtrs, const uint32_t* srcSizes, uint32_t nChunks,
                                         uint8_t* const* dstPtrs, const uint32_t* dstCaps, int32_t* outSizes,
                                         const uint8_t* const* dictPtrs, const uint32_t* dictSizes, uint32_t nDicts,
                                         const uint32_t* chunkDict, hipStream_t st) {
-    constexpr uint32_t kGrid = 1u << 30;
-    for (uint32_t o = 0; o < nChunks;) {
-        const uint32_t g = std::min(nChunks - o, kGrid);
+    return launch_slices(nChunks, kBatchGrid, [&](uint32_t o, uint32_t g) {
         hipLaunchKernelGGL(k_decode_batch_dict_set, dim3(g), dim3(64), 0, st, srcPtrs + o, srcSizes + o, dstPtrs + o,
                            dstCaps + o, outSizes + o, dictPtrs, dictSizes, nDicts, chunkDict + o);
-        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        o += g;
-    }
-    return hipSuccess;
+    });
 }
 #endif
 

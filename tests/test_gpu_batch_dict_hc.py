@@ -1,7 +1,7 @@
 """Batched LZ4-HC compress with a shared dictionary (include/lz4mt_hip.h
 section 5c: lz4mtHipDictPrepareHC, lz4mtHipCompressBatchDictHC; kernels
-k_hc_dict_prepare, k_hc_prev_batch_dict, k_encode_hc_batch_dict,
-k_encode_hc_opt_batch_dict).
+k_hc_dict_prepare, k_hc_prev_batch<HcSharedDict>,
+k_encode_hc_batch<HcSharedDict>, k_encode_hc_opt_batch<HcSharedDict>).
 
 The reference is liblz4 1.9.3 itself, through the committed fixtures
 tests/golden/dict_hc_blocks.json and dict_hc_fuzz.json (LZ4_loadDictHC +

@@ -1,7 +1,7 @@
 """Batched block operators with a set of dictionaries and an index per chunk
 (include/lz4mt_hip.h section 5d: lz4mtHipDictSetPrepare,
 lz4mtHipCompressBatchDictSet, lz4mtHipDecompressBatchDictSet; kernels
-k_dict_set_prepare, k_encode_batch_dict_set, k_decode_batch_dict_set).
+k_dict_set_prepare, k_encode_batch_dict<XC, DictSet>, k_decode_batch_dict_set).
 
 The references are liblz4 1.9.3 through the committed fixture
 tests/golden/dict_blocks.json -- all its dictionaries in ONE call each way --

@@ -1,8 +1,8 @@
 """Batched LZ4-HC compress with a set of dictionaries and an index per chunk
 (include/lz4mt_hip.h section 5e: lz4mtHipDictSetPrepareHC,
 lz4mtHipCompressBatchDictSetHC; kernels k_hc_dict_set_prepare,
-k_hc_prev_batch_dict_set, k_encode_hc_batch_dict_set,
-k_encode_hc_opt_batch_dict_set).
+k_hc_prev_batch<HcDictSet>, k_encode_hc_batch<HcDictSet>,
+k_encode_hc_opt_batch<HcDictSet>).
 
 The reference is liblz4 1.9.3 itself, through the committed fixtures
 tests/golden/dict_hc_blocks.json and dict_hc_fuzz.json (LZ4_loadDictHC +

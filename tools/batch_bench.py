@@ -206,17 +206,18 @@ def batch_row(name, src, sizes, reps, level=0, slots=0, dct=None):
                 dz = timed(dec_s, reps)
                 assert torch.equal(csz, shared_sizes), name   # the same dictionary bytes: the same blocks
                 round_trip()
-                sset = {"dicts": nd, "set_kernel": "k_encode_batch_dict_set / k_decode_batch_dict_set",
+                sset = {"dicts": nd, "set_kernel": "k_encode_batch_dict<DictSet> / k_decode_batch_dict_set",
                         "set_compress_ms": round(es[0], 3),
                         "set_compress_ms_min_max": [round(es[1], 3), round(es[2], 3)],
                         "set_decompress_ms": round(dz[0], 3),
                         "set_decompress_ms_min_max": [round(dz[1], 3), round(dz[2], 3)],
                         "set_compress_over_shared": round(es[0] / ed[0], 4),
                         "set_decompress_over_shared": round(dz[0] / dd[0], 4)}
-        kernel, plain = "k_encode_batch_dict", "k_encode_batch16" if max_chunk < 65547 else "k_encode_batch"
+        kernel, plain = "k_encode_batch_dict<SharedDict>", "k_encode_batch16" if max_chunk < 65547 else "k_encode_batch"
         if level >= 3:
-            kernel = "k_hc_prev_batch_dict + " + ("k_encode_hc_opt_batch_dict" if level >= 10 else "k_encode_hc_batch_dict")
-            plain = "k_hc_prev_batch + " + ("k_encode_hc_opt_batch" if level >= 10 else "k_encode_hc_batch")
+            parse = "k_encode_hc_opt_batch" if level >= 10 else "k_encode_hc_batch"
+            kernel = f"k_hc_prev_batch<HcSharedDict> + {parse}<HcSharedDict>"
+            plain = f"k_hc_prev_batch<HcNoDict> + {parse}<HcNoDict>"
             fast.update({"slots": nslots, "rounds": -(-n // nslots), "workspace_bytes": ws.numel()})
         return {"name": name, "chunks": n, "bytes": total, "max_chunk": max_chunk,
                 "kernel": kernel + " / k_decode_batch_dict", "plain_kernel": plain, **fast, **sset,
@@ -281,8 +282,8 @@ def hc_set_part(name, reps, level, n, max_chunk, nd, copies, d_ptrs, d_sizes, st
     es = timed(enc_s, reps)
     assert torch.equal(csz, shared_sizes), name   # the same dictionary bytes: the same blocks
     return {"dicts": nd,
-            "set_kernel": "k_hc_prev_batch_dict_set + " + ("k_encode_hc_opt_batch_dict_set" if level >= 10 else
-                                                           "k_encode_hc_batch_dict_set"),
+            "set_kernel": "k_hc_prev_batch<HcDictSet> + " + ("k_encode_hc_opt_batch" if level >= 10 else
+                                                            "k_encode_hc_batch") + "<HcDictSet>",
             "set_compress_ms": round(es[0], 3), "set_compress_ms_min_max": [round(es[1], 3), round(es[2], 3)],
             "separate_calls": int((counts > 0).sum()),
             "separate_compress_ms": round(ek[0], 3),
